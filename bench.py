@@ -5,11 +5,23 @@
 A "step" is one pass of the hot path (DetectLanguageSummaryV2 per document,
 compact_lang_det_impl.cc:1707-2106) over one batch of synthetic documents that
 is already resident in HBM.  The headline is C2 (BASELINE.json configs[1]:
-1M ~140-byte tweets on one MI355X); the same run measures the metric's second
-half, C3 (configs[2]: 100K 16 KB pages), as the "c3" sub-object, and the
-host-memory path (cld_detect_batch: pinned staging, chunked upload / kernels /
-download on three streams) on C2 as "host_path".  --config c3/c4/c5 makes
-another config the headline instead.
+1M ~140-byte tweets on one MI355X).  --config c3/c4/c5 makes another config
+the headline instead.
+
+A plain run does only what the headline needs: it builds the batch, warms up,
+times the steps and prints the line ("cpu_baseline", "c3" and "host_path" are
+null).  --full adds the measurements that take runs of their own: the CPU
+baseline with its bit-for-bit check of a sample, the metric's second half, C3
+(configs[2]: 100K 16 KB pages), as the "c3" sub-object, and the host-memory
+path (cld_detect_batch: pinned staging, chunked upload / kernels / download on
+three streams) on C2 as "host_path"; --no-cpu-baseline / --no-sub / --no-host
+drop one of them from a --full run.
+
+--dump-outputs DIR writes what the last timed step left in the result buffer
+(rank 0's shard) as DIR/<field>.npy, one array per field of the result record
+(float32; normalized3 float64), at most 64 MB in all: beyond that a fixed,
+seeded sample of the documents.  The corpus is seeded, so two runs with the
+same arguments score the same bytes.
 
 One process per GPU: `--gpus N` (N > 1) run without a torch.distributed
 environment starts N ranks itself -- it counts the visible GPUs (without
@@ -27,7 +39,7 @@ Tables: the synthetic Q1 quadgram table, opted into explicitly
 default is the empty Q0 table (the real quadchrome table is a missing blob).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
-                    [--no-sub] [--no-host] [--no-cpu-baseline]
+                    [--dump-outputs DIR] [--full [--no-sub] [--no-host] [--no-cpu-baseline]]
 """
 import argparse
 import json
@@ -277,6 +289,24 @@ def measure(cfg_name, n, steps, warmup, rank, dist, be):
     return res, buf, offs, gpu_out
 
 
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: the result records of the last timed step, one .npy per
+    field (float32, which holds every integer field exactly; normalized3
+    float64).  A batch whose arrays would pass DUMP_MAX_BYTES is cut to a
+    fixed, seeded sample of its documents, in document order."""
+    kinds = {f: (np.float64 if out.dtype[f].base.kind == "f" else np.float32) for f in out.dtype.names}
+    per_doc = sum(np.dtype(k).itemsize * int(np.prod(out.dtype[f].shape, dtype=np.int64)) for f, k in kinds.items())
+    keep = DUMP_MAX_BYTES // per_doc
+    if len(out) > keep:
+        out = out[np.sort(np.random.default_rng(0xD0C5).choice(len(out), size=keep, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for f, k in kinds.items():
+        np.save(os.path.join(path, f + ".npy"), np.ascontiguousarray(out[f], dtype=k))
+
+
 def host_path(n, steps, rank):
     """cld_detect_batch from host memory (C2): pageable numpy buffers (page-
     locked for the call, or staged through the runtime's pinned chunk buffers)
@@ -332,13 +362,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--docs", type=int, default=0, help="documents per GPU (default: config size)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<field>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline (and check a sample against it), the C3 sub-object "
+                         "and the host-memory path")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sub", action="store_true", help="skip the C3 sub-measurement of a C2 run")
-    ap.add_argument("--no-host", action="store_true", help="skip the host-memory path measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-sub", action="store_true", help="with --full: skip the C3 sub-measurement of a C2 run")
+    ap.add_argument("--no-host", action="store_true", help="with --full: skip the host-memory path measurement")
     args = ap.parse_args()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 0 or args.warmup < 0:
+        sys.exit("bench.py: --steps and --warmup must be >= 0 (--steps 0: the config's default)")
+    if not args.full:
+        args.no_cpu_baseline = args.no_sub = args.no_host = True
     Backend = backend_class()
 
     if "WORLD_SIZE" not in os.environ:
@@ -363,6 +402,8 @@ def main():
     n = args.docs or cfg["docs"]
     steps = args.steps or cfg["steps"]
     head, buf, offs, gpu_out = measure(args.config, n, steps, args.warmup, rank, dist, be)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, gpu_out)
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.config, buf, offs, gpu_out, args.cpu_seconds,

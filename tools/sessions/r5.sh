@@ -21,7 +21,7 @@ for s in ${STEPS:-suite smoke bench}; do
     suite) step 1000 pytest_gpu.txt python -u -m pytest tests -m gpu -x -v --timeout 400 --timeout-method thread; tail -1 $O/pytest_gpu.txt ;;
     tests) step 600 pytest_sel.txt python -u -m pytest ${PYTESTS} -m gpu -x -v --timeout 200 --timeout-method thread; tail -1 $O/pytest_sel.txt ;;
     smoke) step 300 smoke.txt python -u -c "import __graft_entry__ as g; g.smoke()"; tail -2 $O/smoke.txt ;;
-    bench) step 400 bench.json python bench.py ;;
+    bench) step 400 bench.json python bench.py --full ;;
     lines) for c in c3 c4 c5; do step 400 bench_$c.json python bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-host --no-sub; done ;;
     prof)
       (cd /tmp && step 300 prof_c2.log rocprofv3 --kernel-trace --stats -d $O/prof_c2 -o c2 --output-format csv -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-host --no-sub) || exit 1

@@ -29,7 +29,7 @@ for s in ${STEPS:-suite smoke bench}; do
     diag) step 150 diag.txt python -u tools/diag_batch.py ;;
     tests) step 600 pytest_sel.txt python -u -m pytest ${PYTESTS} -m gpu -x -v --timeout 200 --timeout-method thread; tail -1 $O/pytest_sel.txt ;;
     smoke) step 300 smoke.txt python -u -c "import __graft_entry__ as g; g.smoke()"; tail -2 $O/smoke.txt ;;
-    bench) step 400 bench.json python bench.py ;;
+    bench) step 400 bench.json python bench.py --full ;;
     lines) for c in c3 c4 c5; do step 400 bench_$c.json python bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-host --no-sub; done ;;
     prof)
       (cd /tmp && step 300 prof_c2.log rocprofv3 --kernel-trace --stats -d $O/prof_c2 -o c2 --output-format csv -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-host --no-sub) || exit 1
@@ -57,7 +57,7 @@ for s in ${STEPS:-suite smoke bench}; do
       for t in ${TABS:-language-detector_amd/data/cld2_synth_q1.cldt language-detector_amd/data/variants/cld2_synth_q1_b65536.cldt language-detector_amd/data/variants/cld2_synth_q1_b262144.cldt language-detector_amd/data/variants/cld2_synth_q1_b1048576.cldt}; do
         b=$(basename $t .cldt)
         for c in ${TABCFG:-c2 c3}; do
-          if [ $c = c3 ]; then a="--steps 3 --warmup 1 --no-cpu-baseline"; k="k_l(span|score|group|finish|rep|ong)"; else a="--cpu-seconds 3"; k=k_wave; fi
+          if [ $c = c3 ]; then a="--steps 3 --warmup 1 --no-cpu-baseline"; k="k_l(span|score|group|finish|rep|ong)"; else a="--full --cpu-seconds 3"; k=k_wave; fi
           step 300 tab_${b}_$c.json env CLD_MI355X_TABLES=$R/$t python bench.py --config $c $a --no-host --no-sub
           (cd /tmp && step 120 tab_${b}_pmc_$c.log env CLD_MI355X_TABLES=$R/$t rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --kernel-include-regex "$k" -d $O/tab_${b}_pmc_$c -o $c --output-format csv -- python3 $R/bench.py --config $c --steps 2 --warmup 1 --no-cpu-baseline --no-host --no-sub) || exit 1
         done
