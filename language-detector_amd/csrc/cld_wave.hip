@@ -54,6 +54,11 @@ __device__ __forceinline__ void wsync() {
 }
 
 __device__ __forceinline__ uint64_t lanemask_lt(int lane) { return lane ? (~0ull >> (64 - lane)) : 0ull; }
+// Number of set bits of a wave-uniform mask below this lane (v_mbcnt): a
+// lane's rank among the lanes of a ballot.
+__device__ __forceinline__ int below(uint64_t m) {
+  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
 // The lane id recomputed where a stage starts (v_mbcnt, as volatile asm): the
 // compiler would otherwise hoist the per-lane values derived from it out of
 // the document's span loop and spill them to scratch (8 waves/SIMD leave 64
@@ -183,6 +188,7 @@ struct Smem {
   };
   union alignas(16) {                 // stage-local arrays
     uint16_t nx[CAP];                 // load: p + ScanToLetterOrSpecial(p, L - p)
+    uint32_t low[CAP];                // load -> first span: lowered character starting here (pack_lowered)
     uint16_t nxq[C::LB];              // quad hits: next quad start for a quad starting at p
     uint16_t wsp[C::NB + 1];          // octa hits: word-ending spaces
     struct {                          // scoring: base emissions (offset, langprob), linear order
@@ -222,6 +228,14 @@ __device__ __forceinline__ int cpt_index(uint32_t b0, uint32_t b1, uint32_t b2, 
   return 2176 + (int)((b0 & 0x0F) << 12 | (b1 & 0x3F) << 6 | (b2 & 0x3F));
 }
 
+// A T.cpt entry as span_lowered keeps it, one register: the lowered bytes
+// (<= 3) | their count << 24, or 0xFFFFFFFF when the table cannot lower the
+// character in that form (bit 10 clear, 4 output bytes, or no entry read).
+__device__ __forceinline__ uint32_t pack_lowered(uint64_t e) {
+  const uint32_t olen = (uint32_t)(e >> 11) & 15;
+  return (((e >> 10) & 1) && olen <= 3) ? (((uint32_t)(e >> 32) & 0xFFFFFFu) | olen << 24) : 0xFFFFFFFFu;
+}
+
 // ------------------------------------------------------- stage 0: document
 // Loads the document, computes script numbers and scanner stops per byte
 // and checks that the per-character formulation below reproduces the
@@ -230,7 +244,8 @@ __device__ __forceinline__ int cpt_index(uint32_t b0, uint32_t b1, uint32_t b2, 
 // scan result of the next character.
 template <int CAP>
 __device__ bool load_document(const DevTables& T, const uint8_t* __restrict__ g, int L, Smem<CAP>& s, int lane,
-                              const uint8_t* __restrict__ hf) {
+                              const uint8_t* __restrict__ hf, bool& lowv) {
+  lowv = false;                          // s.a.low holds every character's pack_lowered (the fast path)
   using C = Cfg<CAP>;
   static_assert(CAP == 256 && C::DOC == 288, "one aligned dword per lane covers the document");
   {
@@ -300,6 +315,7 @@ __device__ bool load_document(const DevTables& T, const uint8_t* __restrict__ g,
       const int st = (int)((e >> 8) & 3);
       slow |= st == 3 ? 1 : 0;
       s.sn[p] = (uint8_t)e;
+      s.a.low[p] = pack_lowered(e);
       const uint64_t m = __ballot(st == 1 && (e & 0xFF) != 0);
       if (lane == 0) s.lsm[w] = m;                      // (a lane-indexed register array would live in scratch)
     }
@@ -307,6 +323,7 @@ __device__ bool load_document(const DevTables& T, const uint8_t* __restrict__ g,
     if (__ballot(slow != 0) == 0) {
       if (lane < 4) s.sn[L + lane] = (uint8_t)script_num(T, dv, L + lane);
       wsync();
+      lowv = true;
       return true;
     }
   }
@@ -554,6 +571,125 @@ __device__ int lower_span(const DevTables& T, Smem<CAP>& s, int text_bytes, int 
   return obase - 3;
 }
 
+// Stages 1 + 2 in one pass (as k_long's span builder): next_span's event logic
+// unchanged, but a kept lead byte contributes its lowered bytes from the
+// property table, a kept continuation byte nothing and a separator one space,
+// so one prefix sum per window places the lowered text directly in lbuf -- no
+// raw copy in sbuf, no second table gather per window.  The first span of a
+// document reads what load_document's gathers left in s.a.low (lowv); a later
+// one, after the hit stages have reused s.a, gathers again, every window
+// before the first is used.  A span that keeps a character the table cannot
+// lower in this form (bit 10 clear, 4 output bytes, or not a well-formed 1-3
+// byte sequence) is redone by next_span + lower_span, unchanged.
+// Returns the lowered text_bytes, 0 = no further span, -1 = re-queue.
+template <int CAP>
+__device__ int span_lowered(const DevTables& T, Smem<CAP>& s, int L, int& next, int& ulscript, int lane, bool lowv) {
+  lane = lane_here();
+  using C = Cfg<CAP>;
+  const int common = (int)T.common, inherited = (int)T.inherited;
+  const int q = find_first<C::NM>(s.lsm, next, L);
+  if (q >= L) { next = L; return 0; }
+  const int spanscript = ufl(s.sn[q]);
+  ulscript = spanscript;
+  // per window, one register: lowered bytes (<= 3) | length << 24; 0xFFFFFFFF = not lowerable here
+  uint32_t ev[C::NM];
+  if (lowv) {                                           // (uniform) load_document's gathers are still there
+#pragma unroll
+    for (int w = 0; w < C::NM; ++w) ev[w] = s.a.low[w * 64 + lane];
+  } else {
+    int idx[C::NM];
+#pragma unroll
+    for (int w = 0; w < C::NM; ++w) {
+      const int p = w * 64 + lane;                      // (the document is zero-padded to DOC bytes)
+      const uint32_t c = s.doc[p], b1 = s.doc[p + 1], b2 = s.doc[p + 2];
+      const int n = utf8_len((uint8_t)c);
+      const bool wf = p >= q && p < L && (c & 0xC0) != 0x80 && n <= 3 && (n < 2 || (b1 & 0xC0) == 0x80) &&
+                      (n < 3 || (b2 & 0xC0) == 0x80);
+      idx[w] = wf ? cpt_index(c, b1, b2, n) : -1;
+    }
+    uint64_t raw[C::NM];
+#pragma unroll
+    for (int w = 0; w < C::NM; ++w) raw[w] = idx[w] >= 0 ? gld(T.cpt + idx[w]) : 0ull;
+#pragma unroll
+    for (int w = 0; w < C::NM; ++w) ev[w] = pack_lowered(raw[w]);
+  }
+  // e0 is the current window's register: the four rotate as the loop advances
+  // (an array picked by the window number would be indexed in scratch)
+  static_assert(C::NM == 4, "four windows");
+  uint32_t e0 = ev[0], e1 = ev[1], e2 = ev[2], e3 = ev[3];
+  for (int i = q >> 6; i > 0; --i) { e0 = e1; e1 = e2; e2 = e3; }
+  if (lane == 0) s.lbuf[0] = ' ';
+  int put = 1, take = L, bad = 0;
+  bool run = true;                                   // q is an O event
+  for (int w = q >> 6; w < C::NM && w * 64 < L; ++w) {
+    const int x = w * 64 + lane;
+    const bool valid = x >= q && x < L;
+    const uint32_t c = valid ? s.doc[x] : 0u;
+    const bool lead = valid && (c & 0xC0) != 0x80;
+    bool brk = false, ok = false, foreign = false;
+    if (lead) {
+      const int sc = s.sn[x];
+      if (sc != spanscript && sc != inherited) {
+        if (sc == common) {
+          brk = true;
+        } else {
+          // (a lookahead onto a rewritten HTML entity sees the raw '&': script 0)
+          const int xn = x + utf8_len((uint8_t)c);
+          const int sc2 = (xn < 64 * C::NM && ((s.ent[xn >> 6] >> (xn & 63)) & 1)) ? 0 : s.sn[xn];
+          brk = sc2 != common && sc2 != spanscript;
+        }
+      }
+      if ((s.lsm[w] >> lane) & 1) {
+        if (sc == spanscript || sc == inherited) ok = true;
+        else foreign = true;
+      }
+    }
+    // next_span's inrun / prev_run on wave-uniform masks: the state after
+    // position i is O_i | (!event_i & state_{i-1}), the carry recurrence of an
+    // adder with generate O and propagate ~events -- so the carries into each
+    // bit of (O | ~events) + O + run are prev_run, and one step more inrun.
+    const uint64_t Bm = __ballot(brk), Om = __ballot(ok), Fm = __ballot(foreign), Lm = __ballot(lead);
+    const uint64_t evm = Bm | Om;
+    const uint64_t ca = Om | ~evm;
+    const uint64_t prevm = (ca + Om + (run ? 1ull : 0ull)) ^ ca ^ Om;
+    const uint64_t runm = Om | (~evm & prevm);
+    const uint64_t Em = Fm & (Bm | ~prevm);            // F while in a gap: the span ends here
+    const int stop = Em ? __builtin_ctzll(Em) : 64;
+    const uint64_t lt_stop = Em ? (Em & (0 - Em)) - 1 : ~0ull, le_stop = Em ? (Em ^ (Em - 1)) : ~0ull;
+    const bool cl = ((Lm & runm & lt_stop) >> lane) & 1;    // a kept character: its lowered bytes
+    const bool sep = ((Bm & prevm & le_stop) >> lane) & 1;  // (never both: a B event ends the run)
+    const uint32_t e = e0;
+    const bool low = e != 0xFFFFFFFFu;
+    bad |= (cl && !low) ? 1 : 0;
+    const int olen = sep ? 1 : (cl && low) ? (int)(e >> 24) : 0;
+    const uint32_t o = sep ? (uint32_t)' ' : e;
+    const int pos = put + excl_scan(olen, lane);
+    put = rdl(pos + olen, 63);
+    if (put + 8 > C::LB - 16) { bad = 1; break; }      // (uniform; lower_span's LB check, closing bytes included)
+    for (int k = 0; k < olen; ++k) s.lbuf[pos + k] = (uint8_t)(o >> (8 * k));
+    if (stop < 64) {
+      take = w * 64 + stop;
+      run = false;
+      break;
+    }
+    run = (runm >> 63) != 0;
+    e0 = e1; e1 = e2; e2 = e3;
+  }
+  if (__ballot(bad != 0)) {
+    const int tb = next_span<CAP>(T, s, L, next, ulscript, lane);
+    return lower_span<CAP>(T, s, tb, lane);
+  }
+  if (run) {                                         // the document ended inside a run
+    if (lane == 0) s.lbuf[put] = ' ';
+    ++put;
+  }
+  // "   \0" and the hash read pad
+  if (lane < 23) s.lbuf[put + lane] = lane < 3 ? ' ' : 0;
+  next = take;
+  wsync();
+  return put;
+}
+
 // QuadHashV2 (cldutil_shared.cc:167-202, the same arithmetic as quad_hash_v2)
 // of the n bytes at LDS text position p: the words at p, p+4, p+8 from four
 // aligned dword reads, the bytes before and after from two byte reads.
@@ -615,7 +751,7 @@ __device__ int quad_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, i
     const bool isws = in && (p == start || text[p - 1] == ' ');
     const uint64_t m = __ballot(isws);
     if (isws) {
-      const int k = nws + __popcll(m & lanemask_lt(lane));
+      const int k = nws + below(m);
       if (k < C::NB) s.qws[k] = (uint16_t)p;
     }
     nws += __popcll(m);
@@ -642,7 +778,7 @@ __device__ int quad_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, i
   for (int w = start >> 6; w * 64 < limit; ++w) {
     const uint64_t m = ufl64(*reinterpret_cast<const uint64_t*>(&s.qmark[2 * w]));
     if ((m >> lane) & 1) {
-      const int k = n + __popcll(m & lanemask_lt(lane));
+      const int k = n + below(m);
       if (k < C::NB) s.qchn[k] = (uint16_t)(w * 64 + lane);
     }
     n += __popcll(m);
@@ -707,7 +843,7 @@ __device__ int quad_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, i
       A = rdlu(hv, t1);
     }
     if ((k >> lane) & 1) {
-      const int kk = base + __popcll(k & lanemask_lt(lane));
+      const int kk = base + below(k);
       s.b_off[kk] = (uint16_t)cp[r];
       s.b_ind[kk] = pr;
     }
@@ -734,7 +870,7 @@ __device__ bool octa_hits(const DevTables& T, Smem<CAP>& s, int limit_next, int&
     const bool sp = p < lim && text[p] == ' ';
     const uint64_t m = __ballot(sp);
     if (sp) {
-      int k = nw + __popcll(m & lanemask_lt(lane));
+      int k = nw + below(m);
       if (k < C::NB) s.a.wsp[k] = (uint16_t)p;
     }
     nw += __popcll(m);
@@ -821,9 +957,10 @@ __device__ bool octa_hits(const DevTables& T, Smem<CAP>& s, int limit_next, int&
       xp = octa_lookup(T.distinctocta, wh[r]);
       dp = octa_lookup(T.deltaocta, wh[r]);
     }
-    const int cx = (pp != 0) + (xp != 0), cd = (dp != 0);
-    const int ox = xb + excl_scan(cx, lane), od = db + excl_scan(cd, lane);
-    const int tx = rdl(ox + cx, 63) - xb, td = rdl(od + cd, 63) - db;
+    // a lane's slots from the ranks of its flags (ballots, not scans)
+    const uint64_t mp = __ballot(pp != 0), mx = __ballot(xp != 0), md = __ballot(dp != 0);
+    const int ox = xb + below(mp) + below(mx), od = db + below(md);
+    const int tx = __popcll(mp) + __popcll(mx), td = __popcll(md);
     if (xb + tx > C::NX || db + td > C::ND) { over = true; break; }
     int o = ox;
     if (pp) { s.x_off[o] = (uint16_t)pws[r]; s.x_ind[o] = pp & ~T.distinctocta.key_mask; ++o; }
@@ -857,7 +994,7 @@ __device__ int cjk_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, in
     }
     const uint64_t m = __ballot(prop > 0);
     if (prop > 0) {
-      int k = b + __popcll(m & lanemask_lt(lane));
+      int k = b + below(m);
       if (k < C::NB) { s.b_off[k] = (uint16_t)(p + len); s.b_ind[k] = (uint32_t)prop; }
     }
     b += __popcll(m);
@@ -880,11 +1017,11 @@ __device__ int cjk_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, in
     }
     const uint64_t md = __ballot(dp != 0), mx = __ballot(xp != 0);
     if (dp) {
-      int k = dcount + __popcll(md & lanemask_lt(lane));
+      int k = dcount + below(md);
       if (k < C::ND) { s.d_off[k] = (uint16_t)p; s.d_ind[k] = dp & ~T.deltabi.key_mask; }
     }
     if (xp) {
-      int k = xcount + __popcll(mx & lanemask_lt(lane));
+      int k = xcount + below(mx);
       if (k < C::NX) { s.x_off[k] = (uint16_t)p; s.x_ind[k] = xp & ~T.distinctbi.key_mask; }
     }
     dcount += __popcll(md); xcount += __popcll(mx);
@@ -966,9 +1103,10 @@ __device__ bool score_round(const DevTables& T, Smem<CAP>& s, int ulscript, bool
         if (l1 == 0) { l1 = l2; l2 = 0; }
       }
     }
-    const int c = (l1 != 0) + (l2 != 0);
-    const int o = eb + excl_scan(c, lane);
-    eb = rdl(o + c, 63);
+    // a lane's slot from the ranks of its two flags (ballots, not a scan)
+    const uint64_t m1 = __ballot(l1 != 0), m2 = __ballot(l2 != 0);
+    const int o = eb + below(m1) + below(m2);
+    eb += __popcll(m1) + __popcll(m2);
     if (eb > C::NE) return false;
     if (l1) { s.a.e.be_off[o] = (uint16_t)off; s.a.e.be_lp[o] = l1; }
     if (l2) { s.a.e.be_off[o + 1] = (uint16_t)off; s.a.e.be_lp[o + 1] = l2; }
@@ -978,18 +1116,20 @@ __device__ bool score_round(const DevTables& T, Smem<CAP>& s, int ulscript, bool
   for (int j0 = 0; j0 < nd; j0 += 64) {
     const int j = j0 + lane;
     uint32_t lp = j0 == 0 ? dpre : j < nd ? ind_at(dob, s.d_ind[j]) : 0u;
-    const int o = ed + excl_scan(lp != 0, lane);
+    const uint64_t m = __ballot(lp != 0);
+    const int o = ed + below(m);
     uint16_t off = j < nd ? s.d_off[j] : 0;
     if (lp) { s.d_off[o] = off; s.d_ind[o] = lp; }
-    ed = rdl(o + (lp != 0), 63);
+    ed += __popcll(m);
   }
   for (int j0 = 0; j0 < nx; j0 += 64) {
     const int j = j0 + lane;
     uint32_t lp = j0 == 0 ? xpre : j < nx ? ind_at(xob, s.x_ind[j]) : 0u;
-    const int o = ex + excl_scan(lp != 0, lane);
+    const uint64_t m = __ballot(lp != 0);
+    const int o = ex + below(m);
     uint16_t off = j < nx ? s.x_off[j] : 0;
     if (lp) { s.x_off[o] = off; s.x_ind[o] = lp; }
-    ex = rdl(o + (lp != 0), 63);
+    ex += __popcll(m);
   }
   // chunk plan from the base-hit count (ChunkAll :978-1031)
   int K = 0;
@@ -1340,11 +1480,13 @@ struct DocSum {
   int text_bytes;
   bool reliable;
 };
-__device__ __forceinline__ DocSum extract_regs(const DevTables& T, const SlotRegs& r, int total, int lane, double& ns) {
+// relp: every slot's reliability percent rl / (val ? val : 1) where the caller has it already.
+__device__ __forceinline__ DocSum extract_regs(const DevTables& T, const SlotRegs& r, int total, int lane, double& ns,
+                                               const int* relp = nullptr) {
   const int unk = (int)T.unknown_lang;
   const bool valid = lane < 3 && r.key != kUnusedKey && (int)r.key != unk;
   const int bc = valid ? r.val : 0;
-  const int rp = valid ? r.rl / (bc ? bc : 1) : 0;
+  const int rp = valid ? (relp ? *relp : r.rl / (bc ? bc : 1)) : 0;
   ns = (valid && bc > 0) ? (double)((int32_t)((uint32_t)r.sc << 10) / (bc > 0 ? bc : 1)) : 0.0;
   const int b0 = rdl(bc, 0), b1 = rdl(bc, 1), b2 = rdl(bc, 2);
   const int t12 = b0 + b1, t123 = t12 + b2;
@@ -1376,20 +1518,38 @@ __device__ __forceinline__ double rdl_f64(double v, int l) {
 // pass must follow (never when `final`).  best_effort: kCLDFlagBestEffort
 // (:1998-2000, :1493): no unreliable-language removal and no UNKNOWN for a
 // small return percent.
-template <class Mv = NoMove>
+// ONE: a DocTote with exactly one slot in use (a single-language document)
+// skips the close-set gather and the sort -- no pair can merge, and Sort(3)
+// only moves that slot to 0 and sets the unused values to -1.
+template <bool ONE = false, class Mv = NoMove>
 __device__ __forceinline__ int finish_document(const DevTables& T, DocTote& dt, int total, bool final, cld_result* __restrict__ out,
                                int lane, bool best_effort = false, Mv&& mv = Mv{}) {
   SlotRegs r = load_slots(dt, lane);
-  refine_close_pairs_regs(T, r, lane, mv);
-  sort3_regs(r, lane);
+  const uint64_t used = ONE ? __ballot(r.key != kUnusedKey) : 0ull;
+  if (ONE && used != 0 && (used & (used - 1)) == 0) {
+    const int sl = __builtin_ctzll(used);
+    const uint32_t k = rdlu(r.key, sl);
+    const int v = rdl(r.val, sl), sc = rdl(r.sc, sl), rl = rdl(r.rl, sl);
+    const bool l0 = lane == 0;
+    r.key = l0 ? k : (uint32_t)kUnusedKey;
+    r.val = l0 ? v : -1;
+    r.sc = l0 ? sc : 0;
+    r.rl = l0 ? rl : 0;
+  } else {
+    refine_close_pairs_regs(T, r, lane, mv);
+    sort3_regs(r, lane);
+  }
   double ns;
-  DocSum x = extract_regs(T, r, total, lane, ns);
+  // (ONE: the reliability percent of every slot once, for ExtractLangEtc and the unreliable test)
+  const int relp = ONE ? r.rl / (r.val ? r.val : 1) : 0;
+  DocSum x = extract_regs(T, r, total, lane, ns, ONE ? &relp : nullptr);
   const bool good = final || total <= 256 || (x.reliable && x.pct[0] >= 70) ||
                     (x.reliable && x.pct[0] + x.pct[1] >= 93);
   if (!good) return 0;
   if (!best_effort) {
     // RemoveUnreliableLanguages (:997-1101) only when some slot is unreliable
-    const bool unrel = lane < 24 && r.key != kUnusedKey && r.val != 0 && r.rl / (r.val ? r.val : 1) < 41;
+    const bool unrel = lane < 24 && r.key != kUnusedKey && r.val != 0 &&
+                       (ONE ? relp : r.rl / (r.val ? r.val : 1)) < 41;
     if (const uint64_t todo = __ballot(unrel)) {
       remove_unreliable_regs(T, r, todo, lane);
       sort3_regs(r, lane);
@@ -1423,8 +1583,9 @@ template <int CAP>
 __device__ bool detect(const DevTables& T, const uint8_t* __restrict__ g, int L, Smem<CAP>& s, int lane,
                        cld_result* __restrict__ out, unsigned long long* __restrict__ prof, uint32_t cflags,
                        const uint32_t* __restrict__ pri, const uint8_t* __restrict__ hf) {
-  // optional per-stage cycle accounting (CLD_PROFILE_STAGES=1): 0 load, 1 span,
-  // 2 lower, 3 quad/uni, 4 octa/bi, 5 score, 6 document level
+  // optional per-stage cycle accounting (CLD_PROFILE_STAGES=1): 0 load, 1 span
+  // + lower (2 stays 0 since they are one pass), 3 quad/uni, 4 octa/bi,
+  // 5 score, 6 document level
   long long t_stage = prof ? (long long)clock64() : 0;
   auto mark = [&](int st) {
     if (prof) {
@@ -1444,7 +1605,8 @@ __device__ bool detect(const DevTables& T, const uint8_t* __restrict__ g, int L,
     }
     return true;
   }
-  if (!load_document<CAP>(T, g, L, s, lane, hf)) return false;
+  bool lowv;
+  if (!load_document<CAP>(T, g, L, s, lane, hf, lowv)) return false;
   mark(0);
   if (lane == 0) s.dt.init();
   if (lane < 8) s.ring[lane >> 2][lane & 3] = 0;
@@ -1452,11 +1614,9 @@ __device__ bool detect(const DevTables& T, const uint8_t* __restrict__ g, int L,
   int next = 0, total = 0;
   for (;;) {
     int ulscript = 0;
-    int tb = next_span<CAP>(T, s, L, next, ulscript, lane);
+    const int tb = span_lowered<CAP>(T, s, L, next, ulscript, lane, lowv);
     mark(1);
     if (tb == 0) break;
-    tb = lower_span<CAP>(T, s, tb, lane);
-    mark(2);
     if (tb < 0) return false;
     int rt = rtype_of(T, ulscript);
     if ((cflags & kCLDFlagScoreAsQuads) && rt != RTypeCJK) rt = RTypeMany;   // scoreonescriptspan.cc:1318-1320
@@ -1465,6 +1625,7 @@ __device__ bool detect(const DevTables& T, const uint8_t* __restrict__ g, int L,
       wsync();
     } else {
       const bool cjk = rt == RTypeCJK;
+      lowv = false;                      // the hit stages and scoring reuse s.a
       int nb = 0, nd = 0, nx = 0, endo;
       if (cjk) {
         endo = cjk_hits<CAP>(T, s, tb, nb, nd, nx, lane);
@@ -1484,7 +1645,7 @@ __device__ bool detect(const DevTables& T, const uint8_t* __restrict__ g, int L,
     }
     total += tb;
   }
-  const int ok = finish_document(T, s.dt, total, false, out, lane, (cflags & kCLDFlagBestEffort) != 0);
+  const int ok = finish_document<true>(T, s.dt, total, false, out, lane, (cflags & kCLDFlagBestEffort) != 0);
   mark(6);
   return ok != 0;
 }
