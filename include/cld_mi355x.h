@@ -66,6 +66,30 @@ typedef struct cld_result {
  * (getonescriptspan.cc:150-541, 592-1027), lang= attributes in the first 8 KB
  * become hints (compact_lang_det_impl.cc:1596-1611). */
 #define CLD_FLAG_HTML 4u
+/* The reference's checked entry points (DetectLanguageCheckUTF8,
+ * compact_lang_det.h:168 / compact_lang_det.cc:44-56;
+ * ExtDetectLanguageSummaryCheckUTF8, compact_lang_det.h:295 /
+ * compact_lang_det.cc:317-355): each document first goes through
+ * SpanInterchangeValid (compact_lang_det_impl.cc:72-80), and one that is not
+ * interchange-valid UTF-8 from its first byte to its last is not scored.  It
+ * gets the result those entries return before they score anything:
+ * lang3 = {26, 26, 26} (UNKNOWN_LANGUAGE), summary_lang 26, percent3 0,
+ * normalized3 0.0, text_bytes 0, is_reliable 0 -- and in vector mode an empty
+ * chunk vector.  The unchecked entries are for input proven valid
+ * (compact_lang_det.h:74): on ill-formed bytes the reference is undefined
+ * (lead bytes C0, C1, F5-F7 index past its tables), and here such a document
+ * takes the slowest path, the sequential span source.  Pass this flag for
+ * input nobody has validated -- crawled pages, user text.
+ * Interchange valid = well-formed UTF-8 (no overlong forms, no surrogates,
+ * nothing above U+10FFFF) without the C0 controls other than TAB LF FF CR
+ * (NUL is rejected), U+007F-U+009F, U+FDD0-U+FDEF and U+nFFFE / U+nFFFF.
+ * With STRIP_EXTRAS / CSTRING the check applies to the prepared text, the
+ * buffer CLD2 would be handed.  The flag belongs to the preparation flags:
+ * a batch that carries it takes the streamed path (a GPU pass over the text
+ * in front of the kernels), never the one-launch path of request-sized
+ * batches nor the coalescer's tiny groups.  The check is a GPU kernel
+ * (cld_valid.hip); documents longer than INT32_MAX bytes give CLD_EINVAL. */
+#define CLD_FLAG_CHECK_UTF8 8u
 /* The reference's public result-affecting flags, with the reference's values
  * (compact_lang_det.h:343-349), accepted in the `flags` word of every batch
  * entry point and applied to every document of the batch:
@@ -107,6 +131,15 @@ typedef struct cld_hints {
  * (wrapper.cc:8).  Thread-safe; concurrent callers are coalesced into GPU
  * micro-batches by the runtime. */
 const char* detect_language(const char* text);
+
+/* DetectLanguageCheckUTF8 (compact_lang_det.h:168, compact_lang_det.cc:44-56)
+ * with is_plain_text = true: *valid_prefix_bytes (NULL: not wanted) receives
+ * the number of leading interchange-valid bytes of text; if that is less than
+ * strlen(text) the text is not scored and the code of UNKNOWN_LANGUAGE ("un";
+ * not mapped to "en", as there) is returned -- the check runs on the host
+ * (cld_valid_prefix_host) and a rejected text never reaches the GPU.
+ * Otherwise detect_language(text). */
+const char* detect_language_checked(const char* text, int* valid_prefix_bytes);
 
 /* Optional explicit initialisation.  tables_path NULL -> $CLD_MI355X_TABLES or
  * the blob shipped next to the library.  n_devices <= 0 -> all visible GPUs.
@@ -164,8 +197,9 @@ int cld_stage_cycles(int ctx, uint64_t* cycles16);
  * pinned (CLD_CHUNK_MB scales both).  Request-sized calls (< 16 MB of text)
  * from concurrent callers are coalesced into one GPU batch; a batch of at
  * most 1024 documents of <= 256 bytes takes one upload, one kernel and one
- * download.  flags: 0 or CLD_FLAG_STRIP_EXTRAS / CLD_FLAG_CSTRING and
- * CLD_FLAG_SCORE_AS_QUADS / CLD_FLAG_BEST_EFFORT (above).  Thread-safe. */
+ * download.  flags: 0 or CLD_FLAG_STRIP_EXTRAS / CLD_FLAG_CSTRING /
+ * CLD_FLAG_CHECK_UTF8 and CLD_FLAG_SCORE_AS_QUADS / CLD_FLAG_BEST_EFFORT
+ * (above).  Thread-safe. */
 int cld_detect_batch(const uint8_t* buf, const uint64_t* offsets, size_t n,
                      cld_result* out, uint32_t flags);
 
@@ -173,10 +207,43 @@ int cld_detect_batch(const uint8_t* buf, const uint64_t* offsets, size_t n,
  * batch: `hints` is NULL or one cld_hints per document (CLDHints); flags is
  * the reference's `flags` argument -- CLD_FLAG_SCORE_AS_QUADS,
  * CLD_FLAG_BEST_EFFORT, the ignored debug flags -- plus CLD_FLAG_HTML for
- * is_plain_text = false (all documents are HTML).  Results are the same
- * fields as cld_detect_batch.  Host buffers; blocks. */
+ * is_plain_text = false (all documents are HTML) and CLD_FLAG_CHECK_UTF8.
+ * Results are the same fields as cld_detect_batch.  Host buffers; blocks. */
 int cld_detect_batch_ex(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
                         uint32_t flags, cld_result* out);
+
+/* ExtDetectLanguageSummaryCheckUTF8 (compact_lang_det.h:295,
+ * compact_lang_det.cc:317-355) over a batch: cld_detect_batch_ex with
+ * CLD_FLAG_CHECK_UTF8 forced on, plus valid_prefix[i] (n entries) =
+ * SpanInterchangeValid of document i, its number of leading interchange-valid
+ * bytes -- the document was scored iff that equals its length; else out[i] is
+ * the "rejected" result (CLD_FLAG_CHECK_UTF8 above).  One upload serves the
+ * check and the scoring.  flags: CLD_FLAG_HTML and the public CLD2 flags;
+ * CLD_FLAG_STRIP_EXTRAS / CLD_FLAG_CSTRING give CLD_EINVAL, because the
+ * prefixes index the documents as given.  A document longer than INT32_MAX
+ * bytes gives CLD_EINVAL; n == 0 CLD_OK; CLD_EIO as for cld_detect_batch. */
+int cld_detect_batch_checked(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
+                             uint32_t flags, cld_result* out, int32_t* valid_prefix);
+
+/* SpanInterchangeValid (compact_lang_det_impl.cc:72-80) alone.
+ *   cld_valid_prefix_host    one document on the host, no GPU: its number of
+ *                            leading interchange-valid bytes (CLD_EINVAL if
+ *                            len > INT32_MAX).  A truncated character at the
+ *                            end counts from its lead byte.
+ *   cld_valid_prefix_batch   host buffers, on GPU 0 (like cld_prepare_batch),
+ *                            in pieces of <= 256 MB; blocks until
+ *                            valid_prefix[0..n) is on the host.
+ *   cld_valid_prefix_device  every pointer in device memory of GPU `device`,
+ *                            enqueued on `stream` (NULL: the runtime's);
+ *                            asynchronous, uses none of the context's scratch.
+ *                            The caller keeps documents <= INT32_MAX bytes.
+ * Documents of <= 256 bytes take one wavefront each; longer ones are checked
+ * in 1 KB tiles, one wavefront per tile, 16 bytes per lane, whatever their
+ * length.  n == 0: CLD_OK. */
+int32_t cld_valid_prefix_host(const uint8_t* doc, size_t len);
+int cld_valid_prefix_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, int32_t* valid_prefix);
+int cld_valid_prefix_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                            int32_t* d_valid_prefix, void* stream);
 
 /* ExtDetectLanguageSummary with a ResultChunkVector per document
  * (compact_lang_det.h:324-335): the same results as cld_detect_batch_ex plus
@@ -193,7 +260,8 @@ int cld_detect_batch_ex(const uint8_t* buf, const uint64_t* offsets, size_t n, c
  * working region is redone alone with 8x the room; should that fail too, it
  * gets an empty vector and the call returns CLD_EIO with every other
  * document's result and vector complete.  Every document runs the sequential
- * kernel (not a high-throughput path, as in the reference). */
+ * kernel (not a high-throughput path, as in the reference).
+ * CLD_FLAG_CHECK_UTF8: a rejected document gets an empty vector. */
 int cld_detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
                          uint32_t flags, cld_result* out, cld_chunk* chunks, size_t chunk_cap,
                          uint64_t* chunk_offsets);
@@ -213,8 +281,8 @@ int cld_hint_priors(const uint8_t* doc, size_t len, int is_plain_text, const cld
 int cld_detect_batch_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets,
                             size_t n, cld_result* d_out, void* stream);
 
-/* cld_detect_batch_device with flags (preparation and CLD2 flags, as for
- * cld_detect_batch).  buf_bytes bounds
+/* cld_detect_batch_device with flags (preparation flags, CLD_FLAG_CHECK_UTF8
+ * among them, and CLD2 flags, as for cld_detect_batch).  buf_bytes bounds
  * d_offsets[n] (the prepared copy is staged in a device buffer of
  * buf_bytes + n bytes).  Asynchronous like cld_detect_batch_device. */
 int cld_detect_batch_device_ex(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,

@@ -6,6 +6,10 @@ Mirrors the reference's caller-facing interface for this path:
   prepare_batch(docs, flags)              handlers.go:150-151: StripExtras (handlers.go:198-210)
                                           + the cgo C-string cut, as a GPU kernel
   load_data_from_file(path)               CLD2::loadDataFromFile (run-time tables)
+  detect_batch_checked(docs)              ExtDetectLanguageSummaryCheckUTF8 per document
+                                          (compact_lang_det.cc:317-355) -> (results, valid prefixes)
+  detect_language_checked(text)           DetectLanguageCheckUTF8 (compact_lang_det.cc:44-56)
+  valid_prefix_batch(docs)                SpanInterchangeValid per document, as a GPU kernel
 There is no CPU fallback: if the HIP library or a GPU is missing, calls raise.
 """
 import ctypes
@@ -23,12 +27,15 @@ SYNTH_TABLES = os.path.join(HERE, "data", "cld2_synth_q1.cldt")
 FLAG_STRIP_EXTRAS = 1      # include/cld_mi355x.h CLD_FLAG_STRIP_EXTRAS
 FLAG_CSTRING = 2           # include/cld_mi355x.h CLD_FLAG_CSTRING
 FLAG_HTML = 4              # include/cld_mi355x.h CLD_FLAG_HTML (cld_detect_batch_ex)
+FLAG_CHECK_UTF8 = 8        # include/cld_mi355x.h CLD_FLAG_CHECK_UTF8: documents that are not interchange-valid are not scored
+VALID_TILE = 1024          # csrc/cld_kernels.h kValidTile: the check's tile (documents over VALID_SHORT_MAX bytes)
+VALID_SHORT_MAX = 256      # csrc/cld_kernels.h kValidShortMax
 FLAG_SCORE_AS_QUADS = 0x0100   # CLD_FLAG_SCORE_AS_QUADS = kCLDFlagScoreAsQuads (compact_lang_det.h:343)
 FLAG_BEST_EFFORT = 0x4000      # CLD_FLAG_BEST_EFFORT = kCLDFlagBestEffort (compact_lang_det.h:349)
 UNKNOWN_ENCODING = 23      # encodings.h UNKNOWN_ENCODING
 UNKNOWN_LANGUAGE = 26      # generated_language.h UNKNOWN_LANGUAGE
 LANG_FAILED = 0xFFFF       # include/cld_mi355x.h CLD_LANG_FAILED: a document without a result
-EIO, ENOMEM, ENOSPC = -5, -12, -28   # include/cld_mi355x.h error codes
+EIO, ENOMEM, ENOSPC, EINVAL = -5, -12, -28, -22   # include/cld_mi355x.h error codes
 
 RESULT_DTYPE = np.dtype([("lang3", "<u2", 3), ("summary_lang", "<u2"), ("percent3", "i1", 3),
                          ("is_reliable", "u1"), ("text_bytes", "<i4"), ("normalized3", "<f8", 3)])
@@ -41,7 +48,9 @@ EXPORTS = ("detect_language", "cld_init", "cld_init_device", "cld_shutdown", "cl
            "cld_load_data_from_file", "cld_load_data_from_raw_address", "cld_unload_data",
            "cld_is_data_dynamic", "cld_export_tables", "cld_convert_data_file",
            "cld_detect_batch_device_ex", "cld_prepare_batch", "cld_host_alloc", "cld_host_free",
-           "cld_kernel_times", "cld_detect_batch_ex", "cld_hint_priors", "cld_detect_batch_vec")
+           "cld_kernel_times", "cld_detect_batch_ex", "cld_hint_priors", "cld_detect_batch_vec",
+           "cld_detect_batch_checked", "cld_valid_prefix_host", "cld_valid_prefix_batch",
+           "cld_valid_prefix_device", "detect_language_checked")
 CHUNK_DTYPE = np.dtype([("offset", "<i4"), ("bytes", "<i4"), ("lang1", "<u2"), ("pad", "<u2")])   # cld_chunk
 
 
@@ -125,6 +134,15 @@ def lib():
                                            ctypes.c_void_p]
         L.cld_hint_priors.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(Hints),
                                       ctypes.c_void_p, ctypes.c_void_p]
+        L.cld_detect_batch_checked.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                               ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+        L.cld_valid_prefix_host.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
+        L.cld_valid_prefix_host.restype = ctypes.c_int32
+        L.cld_valid_prefix_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        L.cld_valid_prefix_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                              ctypes.c_void_p, ctypes.c_void_p]
+        L.detect_language_checked.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
+        L.detect_language_checked.restype = ctypes.c_char_p
         _lib = L
     return _lib
 
@@ -257,7 +275,7 @@ def detect_batch(docs=None, buf=None, offsets=None, flags=0, out=None):
 def detect_batch_ex(docs=None, buf=None, offsets=None, hints=None, html=False, flags=0):
     """ExtDetectLanguageSummary per document (compact_lang_det.h:324-335):
     html=True scores every document as HTML (is_plain_text = false); hints is
-    None or one Hints per document; flags: FLAG_SCORE_AS_QUADS / FLAG_BEST_EFFORT."""
+    None or one Hints per document; flags: FLAG_SCORE_AS_QUADS / FLAG_BEST_EFFORT / FLAG_CHECK_UTF8."""
     if docs is not None:
         buf, offsets = pack(docs)
     buf = np.ascontiguousarray(buf, dtype=np.uint8)
@@ -351,6 +369,73 @@ def detect_language(text):
     """main.go:77-81 / wrapper.cc:7-16: NUL-terminated text -> ISO code ('en' for unknown)."""
     b = text.encode("utf-8") if isinstance(text, str) else bytes(text)
     return lib().detect_language(b).decode()
+
+
+def detect_language_checked(text):
+    """DetectLanguageCheckUTF8 (compact_lang_det.cc:44-56) -> (ISO code, valid_prefix_bytes):
+    a text that is not interchange-valid UTF-8 is not scored and gets 'un'."""
+    b = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+    vp = ctypes.c_int(0)
+    code = lib().detect_language_checked(b, ctypes.byref(vp)).decode()
+    return code, vp.value
+
+
+def valid_prefix_host(doc):
+    """SpanInterchangeValid (compact_lang_det_impl.cc:72-80) of one document, on the host (no GPU)."""
+    b = doc.encode("utf-8") if isinstance(doc, str) else bytes(doc)
+    rc = lib().cld_valid_prefix_host(b, len(b))
+    if rc < 0:
+        raise CldError("cld_valid_prefix_host failed: %d" % rc)
+    return rc
+
+
+def valid_prefix_batch(docs=None, buf=None, offsets=None):
+    """SpanInterchangeValid per document on the GPU (cld_valid_prefix_batch) -> int32[n]."""
+    if docs is not None:
+        buf, offsets = pack(docs)
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    vp = np.zeros(n, dtype=np.int32)
+    bptr = buf.ctypes.data if buf.size else ctypes.addressof(ctypes.c_uint8(0))
+    rc = lib().cld_valid_prefix_batch(bptr, offsets.ctypes.data, n, vp.ctypes.data)
+    if rc != 0:
+        raise CldError("cld_valid_prefix_batch failed: %d" % rc)
+    return vp
+
+
+def valid_prefix_device(device, d_buf_ptr, d_offsets_ptr, n, d_valid_prefix_ptr, stream_ptr=None):
+    """cld_valid_prefix_device: every pointer in device memory; asynchronous on the stream."""
+    rc = lib().cld_valid_prefix_device(device, d_buf_ptr, d_offsets_ptr, n, d_valid_prefix_ptr, stream_ptr)
+    if rc != 0:
+        raise CldError("cld_valid_prefix_device failed: %d" % rc)
+
+
+def detect_batch_checked(docs=None, buf=None, offsets=None, hints=None, html=False, flags=0):
+    """ExtDetectLanguageSummaryCheckUTF8 per document (compact_lang_det.cc:317-355) ->
+    (results, valid_prefix int32[n]).  Document i was scored iff valid_prefix[i] is its
+    length; else results[i] is the reference's "rejected" result (UNKNOWN, zeros)."""
+    if docs is not None:
+        buf, offsets = pack(docs)
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    out = np.zeros(n, dtype=RESULT_DTYPE)
+    vp = np.zeros(n, dtype=np.int32)
+    harr = None
+    if hints is not None:
+        if len(hints) != n:
+            raise ValueError("need one Hints per document")
+        harr = (Hints * n)(*hints) if n else None
+    bptr = buf.ctypes.data if buf.size else ctypes.addressof(ctypes.c_uint8(0))
+    rc = lib().cld_detect_batch_checked(bptr, offsets.ctypes.data, n,
+                                        ctypes.cast(harr, ctypes.c_void_p) if harr else None,
+                                        (FLAG_HTML if html else 0) | flags, out.ctypes.data, vp.ctypes.data)
+    if rc == EIO:
+        raise PartialBatchError("cld_detect_batch_checked", (out, vp), out["summary_lang"] == LANG_FAILED)
+    if rc != 0:
+        raise CldError("cld_detect_batch_checked failed: %d" % rc)
+    return out, vp
 
 
 def version():

@@ -115,6 +115,28 @@ hipError_t cld_launch_strip_offsets(const uint8_t* buf, const uint64_t* offs, in
                                     uint64_t* out_offs, void* scratch, hipStream_t s);
 hipError_t cld_launch_strip_write(const uint8_t* buf, const uint64_t* offs, int n, uint32_t flags,
                                   const uint64_t* out_offs, uint8_t* out, hipStream_t s);
+// Exclusive scan of n lengths (scratch[0..n), written by the caller) into
+// out_offs[0..n]; scratch as for cld_launch_strip_offsets.
+hipError_t cld_launch_scan_lengths(int n, uint64_t* out_offs, void* scratch, hipStream_t s);
+// The interchange-valid UTF-8 check (cld_valid.hip; SpanInterchangeValid,
+// compact_lang_det_impl.cc:72-80).  Documents of at most kValidShortMax bytes
+// take one wave each, longer ones go in tiles of kValidTile bytes at
+// kValidTile-aligned addresses.  bytes_hint: offs[n] - offs[0] where the host
+// knows it (it sizes the tile kernels' grid), else 0.
+constexpr int kValidShortMax = 256;
+constexpr int kValidTile = 1024;
+hipError_t cld_launch_valid_prefix(const uint8_t* buf, const uint64_t* offs, int n, int32_t* valid_prefix,
+                                   uint64_t bytes_hint, hipStream_t s);
+// CLD_FLAG_CHECK_UTF8: len[i] = document i's length when valid_prefix[i] says
+// the whole of it is valid, else 0; the valid documents copied to out at
+// out_offs (the scan of len); the reference's "rejected" result written over
+// out[i] (and 0 over n_chunks[i], nullable) for every other document.
+hipError_t cld_launch_valid_lens(const uint64_t* offs, int n, const int32_t* valid_prefix, uint64_t* len,
+                                 hipStream_t s);
+hipError_t cld_launch_valid_copy(const uint8_t* buf, const uint64_t* offs, int n, const uint64_t* out_offs,
+                                 uint8_t* out, uint64_t bytes_hint, hipStream_t s);
+hipError_t cld_launch_valid_fixup(const uint64_t* offs, int n, const int32_t* valid_prefix, cld_result* out,
+                                  int32_t* n_chunks, uint32_t unknown_language, hipStream_t s);
 // fault_doc (k_long): test hook, batch index of a document made to fail
 // (0xFFFFFFFF: none): it gets no result (summary CLD_LANG_FAILED).
 // seq_list (n entries, counters[kCtrRequeue2]): the documents k_long hands to

@@ -32,6 +32,7 @@
 #include "cld_dynamic_data.h"
 #include "cld_hints.h"
 #include "cld_kernels.h"
+#include "cld_valid_rule.h"
 #include "cldt_format.h"
 
 namespace {
@@ -419,6 +420,14 @@ struct Device {
   uint32_t* d_hpos = nullptr; size_t hpos_cap = 0;       //   and (vec mode) each byte's page offset
   uint64_t* d_soffs = nullptr; size_t soffs_cap = 0;
   uint8_t* d_sscr = nullptr; size_t sscr_cap = 0;
+  // CLD_FLAG_CHECK_UTF8 (cld_valid.hip): valid prefixes, and the prepared batch in which a rejected
+  // document is empty.  p_buf / p_offs: where enqueue_prepare left the prepared batch (d_sbuf or d_cbuf);
+  // chk_offs / chk_vp: the offsets and prefixes the check ran on (enqueue_fixup reads them)
+  int32_t* d_vp = nullptr; size_t vp_cap = 0;
+  uint8_t* d_cbuf = nullptr; size_t cbuf_cap = 0;
+  uint64_t* d_coffs = nullptr; size_t coffs_cap = 0;
+  const uint8_t* p_buf = nullptr; const uint64_t* p_offs = nullptr;
+  const uint64_t* chk_offs = nullptr; const int32_t* chk_vp = nullptr;
   hipEvent_t ev[4]{};
   std::vector<std::array<hipEvent_t, 4>> ev_pool;   // one set per enqueue since reset
   size_t ev_used = 0;
@@ -444,8 +453,11 @@ struct Device {
     uint32_t* h_pri = nullptr; size_t h_pri_cap = 0;
     uint8_t* d_sp = nullptr; size_t d_sp_cap = 0;
     uint32_t* d_pri = nullptr; size_t d_pri_cap = 0;
+    int32_t* d_vp = nullptr; size_t d_vp_cap = 0;        // CLD_FLAG_CHECK_UTF8: the chunk's valid prefixes
+    int32_t* h_vp = nullptr; size_t h_vp_cap = 0;        //   and their pinned copy (cld_detect_batch_checked)
     hipEvent_t up = nullptr, comp = nullptr, down = nullptr;
     size_t pending_n = 0; cld_result* pending_dst = nullptr;   // results to hand over once `down` fires
+    int32_t* pending_vp = nullptr;
     bool busy = false;
   } hs[2];
   hipStream_t up_stream = nullptr, down_stream = nullptr;
@@ -674,7 +686,9 @@ int init_device(Device* d) {
   return CLD_OK;
 }
 
-constexpr uint32_t kPrepFlags = CLD_FLAG_STRIP_EXTRAS | CLD_FLAG_CSTRING;
+constexpr uint32_t kStripFlags = CLD_FLAG_STRIP_EXTRAS | CLD_FLAG_CSTRING;
+// flags that put a preparation step in front of the kernels (such batches take the streamed path)
+constexpr uint32_t kPrepFlags = kStripFlags | CLD_FLAG_CHECK_UTF8;
 // the reference's public flags the kernels apply; its debug-output flags are accepted and ignored
 constexpr uint32_t kCldFlags = CLD_FLAG_SCORE_AS_QUADS | CLD_FLAG_BEST_EFFORT;
 constexpr uint32_t kPublicFlags = kCldFlags | CLD_FLAG_DEBUG_MASK;
@@ -716,16 +730,56 @@ uint32_t heavy_kb() {
   return v;
 }
 
-// Text preparation (handlers.go:150-151) on device d: documents [buf, offs) ->
-// prepared documents in d->d_sbuf / d->d_soffs.  cap_bytes bounds offs[n].
+// Text preparation on device d: documents [buf, offs) -> prepared documents at
+// d->p_buf / d->p_offs.  cap_bytes bounds offs[n].
+//  * CLD_FLAG_STRIP_EXTRAS / CSTRING (handlers.go:150-151): into d_sbuf / d_soffs;
+//  * CLD_FLAG_CHECK_UTF8 (compact_lang_det.cc:330-334), on the text the step
+//    above left: valid prefixes into vp (n entries; nullptr: d_vp), then a copy
+//    in d_cbuf / d_coffs in which every rejected document is empty, so no
+//    scoring kernel reads an ill-formed byte.  enqueue_fixup, after the
+//    kernels, gives those documents the reference's "rejected" result.
 int enqueue_prepare(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, uint64_t cap_bytes,
-                    uint32_t flags, hipStream_t s) {
+                    uint32_t flags, hipStream_t s, int32_t* vp = nullptr) {
   HIP_OK(hipStreamWaitEvent(s, d->done, 0));   // the previous batch may still read d_sbuf
-  if (grow(&d->d_sbuf, &d->sbuf_cap, std::max<size_t>(cap_bytes + n, 1))) return CLD_ENOMEM;
-  if (grow(&d->d_soffs, &d->soffs_cap, n + 1)) return CLD_ENOMEM;
   if (grow(&d->d_sscr, &d->sscr_cap, cld_strip_scratch_bytes((int)n))) return CLD_ENOMEM;
-  HIP_OK(cld_launch_strip_offsets(buf, offs, (int)n, flags & kPrepFlags, d->d_soffs, d->d_sscr, s));
-  HIP_OK(cld_launch_strip_write(buf, offs, (int)n, flags & kPrepFlags, d->d_soffs, d->d_sbuf, s));
+  const uint8_t* src = buf;
+  const uint64_t* so = offs;
+  if ((flags & kStripFlags) || !(flags & CLD_FLAG_CHECK_UTF8)) {   // (neither flag: a plain copy, cld_prepare_batch)
+    if (grow(&d->d_sbuf, &d->sbuf_cap, std::max<size_t>(cap_bytes + n, 1))) return CLD_ENOMEM;
+    if (grow(&d->d_soffs, &d->soffs_cap, n + 1)) return CLD_ENOMEM;
+    HIP_OK(cld_launch_strip_offsets(buf, offs, (int)n, flags & kStripFlags, d->d_soffs, d->d_sscr, s));
+    HIP_OK(cld_launch_strip_write(buf, offs, (int)n, flags & kStripFlags, d->d_soffs, d->d_sbuf, s));
+    src = d->d_sbuf;
+    so = d->d_soffs;
+  }
+  if (flags & CLD_FLAG_CHECK_UTF8) {
+    if (!vp) {
+      if (grow(&d->d_vp, &d->vp_cap, std::max<size_t>(n, 1))) return CLD_ENOMEM;
+      vp = d->d_vp;
+    }
+    if (grow(&d->d_cbuf, &d->cbuf_cap, std::max<size_t>(cap_bytes + n, 1))) return CLD_ENOMEM;
+    if (grow(&d->d_coffs, &d->coffs_cap, n + 1)) return CLD_ENOMEM;
+    HIP_OK(cld_launch_valid_prefix(src, so, (int)n, vp, cap_bytes + n, s));
+    HIP_OK(cld_launch_valid_lens(so, (int)n, vp, (uint64_t*)d->d_sscr, s));
+    HIP_OK(cld_launch_scan_lengths((int)n, d->d_coffs, d->d_sscr, s));
+    HIP_OK(cld_launch_valid_copy(src, so, (int)n, d->d_coffs, d->d_cbuf, cap_bytes + n, s));
+    d->chk_offs = so;
+    d->chk_vp = vp;
+    src = d->d_cbuf;
+    so = d->d_coffs;
+  }
+  d->p_buf = src;
+  d->p_offs = so;
+  return CLD_OK;
+}
+
+// After the kernels of a CLD_FLAG_CHECK_UTF8 batch: the reference's result for
+// a rejected document (UNKNOWN_LANGUAGE, nothing scored, not reliable) over
+// out[i] for every document enqueue_prepare rejected; n_chunks (vector mode,
+// else nullptr): 0 chunks for those.
+int enqueue_fixup(Device* d, cld_result* out, size_t n, hipStream_t s, int32_t* n_chunks = nullptr) {
+  HIP_OK(cld_launch_valid_fixup(d->chk_offs, (int)n, d->chk_vp, out, n_chunks, g_tab.meta.unknown_language, s));
+  HIP_OK(hipEventRecord(d->done, s));          // (it reads the prepare step's offsets and prefixes)
   return CLD_OK;
 }
 
@@ -1075,7 +1129,8 @@ struct HostReg {
 constexpr int kDocsFailed = 1;
 
 int run_host_stream(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, cld_result* out, uint32_t flags,
-                    const uint8_t* special = nullptr, const uint32_t* priors = nullptr, bool html = false) {
+                    const uint8_t* special = nullptr, const uint32_t* priors = nullptr, bool html = false,
+                    int32_t* vp_out = nullptr) {
   std::lock_guard<std::mutex> lk(d->mu);
   HIP_OK(hipSetDevice(d->id));
   d->ev_used = 0;
@@ -1139,6 +1194,8 @@ int run_host_stream(Device* d, const uint8_t* buf, const uint64_t* offs, size_t 
     if (!r && special) r = grow_host(&h.h_sp, &h.h_sp_cap, max_m);
     if (!r && priors) r = grow(&h.d_pri, &h.d_pri_cap, 16 * max_m);
     if (!r && priors) r = grow_host(&h.h_pri, &h.h_pri_cap, 16 * max_m);
+    if (!r && (flags & CLD_FLAG_CHECK_UTF8)) r = grow(&h.d_vp, &h.d_vp_cap, std::max<size_t>(max_m, 1));
+    if (!r && vp_out) r = grow_host(&h.h_vp, &h.h_vp_cap, std::max<size_t>(max_m, 1));
     if (r) return r;
   }
   int rc = CLD_OK;
@@ -1146,6 +1203,7 @@ int run_host_stream(Device* d, const uint8_t* buf, const uint64_t* offs, size_t 
     if (!h.busy) return CLD_OK;
     HIP_OK(hipEventSynchronize(h.down));
     if (h.pending_dst && h.pending_dst != h.h_out) par_copy(h.pending_dst, h.h_out, h.pending_n * sizeof(cld_result));
+    if (h.pending_vp) memcpy(h.pending_vp, h.h_vp, h.pending_n * sizeof(int32_t));
     h.busy = false;
     return CLD_OK;
   };
@@ -1202,9 +1260,13 @@ int run_host_stream(Device* d, const uint8_t* buf, const uint64_t* offs, size_t 
       }
     }
     if (flags & kPrepFlags) {
-      if ((rc = enqueue_prepare(d, kbuf, h.d_offs, m, bytes, flags, d->stream))) break;
-      rc = enqueue(d, d->d_sbuf, d->d_soffs, m, h.d_out, d->stream, nullptr, nullptr, flags, 0, 0,
+      // (the prepared batch's offsets start at 0: HTML pages are rewritten with base 0)
+      const bool chk = (flags & CLD_FLAG_CHECK_UTF8) != 0;
+      if ((rc = enqueue_prepare(d, kbuf, h.d_offs, m, bytes, flags, d->stream, chk ? h.d_vp : nullptr))) break;
+      rc = enqueue(d, d->p_buf, d->p_offs, m, h.d_out, d->stream, special ? h.d_sp : nullptr,
+                   (special && priors) ? h.d_pri : nullptr, flags, 0, (special && html) ? bytes : 0,
                    d->d_ctrs + c * kCtrSlots, long_hint);
+      if (rc == CLD_OK && chk) rc = enqueue_fixup(d, h.d_out, m, d->stream);
     } else {
       rc = enqueue(d, kbuf, h.d_offs, m, h.d_out, d->stream, special ? h.d_sp : nullptr,
                    (special && priors) ? h.d_pri : nullptr, flags, base, (special && html) ? bytes : 0,
@@ -1217,8 +1279,11 @@ int run_host_stream(Device* d, const uint8_t* buf, const uint64_t* offs, size_t 
     HIP_BRK(hipStreamWaitEvent(d->down_stream, h.comp, 0))
     HIP_BRK(hipMemcpyAsync(out_pinned ? dst : h.h_out, h.d_out, m * sizeof(cld_result), hipMemcpyDeviceToHost,
                           d->down_stream))
+    if (vp_out)
+      HIP_BRK(hipMemcpyAsync(h.h_vp, h.d_vp, m * sizeof(int32_t), hipMemcpyDeviceToHost, d->down_stream))
     HIP_BRK(hipEventRecord(h.down, d->down_stream))
     h.pending_n = m;
+    h.pending_vp = vp_out ? vp_out + a : nullptr;
     h.pending_dst = out_pinned ? nullptr : dst;
     h.busy = true;
   }
@@ -1400,9 +1465,10 @@ int run_tiny(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, cld_
 
 // One device's share of a host batch: run_tiny when it qualifies, else the streamed path.
 int run_host_shard(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, cld_result* out, uint32_t flags,
-                   const uint8_t* special = nullptr, const uint32_t* priors = nullptr, bool html = false) {
+                   const uint8_t* special = nullptr, const uint32_t* priors = nullptr, bool html = false,
+                   int32_t* vp_out = nullptr) {
   if (tiny_batch(d, offs, n, flags, special, priors)) return run_tiny(d, buf, offs, n, out, flags);
-  return run_host_stream(d, buf, offs, n, out, flags, special, priors, html);
+  return run_host_stream(d, buf, offs, n, out, flags, special, priors, html, vp_out);
 }
 
 // Documents the kernels could not score come back marked CLD_LANG_FAILED
@@ -1417,8 +1483,9 @@ int run_host_shard(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n
 constexpr size_t kIsolateAlone = 16;
 int run_host_shard_isolating(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, cld_result* out,
                              uint32_t flags, const uint8_t* special = nullptr, const uint32_t* priors = nullptr,
-                             bool html = false) {
-  int rc = run_host_shard(d, buf, offs, n, out, flags, special, priors, html);
+                             bool html = false, int32_t* vp_out = nullptr) {
+  // (vp_out: the valid prefixes of a checked batch; the first run delivers them, the retries below only score)
+  int rc = run_host_shard(d, buf, offs, n, out, flags, special, priors, html, vp_out);
   if (rc != kDocsFailed) return rc;
   std::vector<size_t> idx;
   for (size_t i = 0; i < n; ++i)
@@ -1523,6 +1590,19 @@ int run_vec_shard(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n,
     if (sp) HIP_OK(hipMemcpyAsync(V.sp, sp, m, hipMemcpyHostToDevice, s));
     if (pr) HIP_OK(hipMemcpyAsync(V.pri, pr, 16 * m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     HIP_OK(hipMemsetAsync(d->d_counters, 0, kCtrSlots * sizeof(uint32_t), s));
+    // CLD_FLAG_CHECK_UTF8: the kernels get the prepared batch, in which a
+    // rejected document is empty (a valid one is a copy: its chunk offsets
+    // index the document as given either way)
+    const bool chk = (cflags & CLD_FLAG_CHECK_UTF8) != 0;
+    const uint8_t* kb = V.in - base;
+    const uint64_t* ko = V.offs;
+    uint64_t kbase = base;
+    if (chk) {
+      if (int rc = enqueue_prepare(d, kb, ko, m, bytes, CLD_FLAG_CHECK_UTF8, s)) return rc;
+      kb = d->p_buf;
+      ko = d->p_offs;
+      kbase = 0;
+    }
     {
       if (grow(&d->d_requeue, &d->requeue_cap, m) || grow(&d->d_requeue2, &d->requeue2_cap, m) ||
           grow(&d->d_lsorted, &d->lsorted_cap, m) || grow(&d->d_lkey, &d->lkey_cap, m))
@@ -1538,19 +1618,22 @@ int run_vec_shard(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n,
             grow(&d->d_hflag, &d->hflag_cap, std::max<size_t>(bytes, 1)) ||
             grow(&d->d_hpos, &d->hpos_cap, 2 * std::max<size_t>(bytes, 1)))
           return CLD_ENOMEM;
-        hb = d->d_hbuf - base;
-        hf = d->d_hflag - base;
-        hpz = d->d_hpos - base;
-        hgz = d->d_hpos + std::max<size_t>(bytes, 1) - base;
-        HIP_OK(cld_launch_html_rewrite(d->d_T, V.in - base, V.offs, (int)m, V.sp, const_cast<uint8_t*>(hb),
+        hb = d->d_hbuf - kbase;
+        hf = d->d_hflag - kbase;
+        hpz = d->d_hpos - kbase;
+        hgz = d->d_hpos + std::max<size_t>(bytes, 1) - kbase;
+        HIP_OK(cld_launch_html_rewrite(d->d_T, kb, ko, (int)m, V.sp, const_cast<uint8_t*>(hb),
                                        const_cast<uint8_t*>(hf), const_cast<uint32_t*>(hpz),
                                        const_cast<uint32_t*>(hgz), 0, nullptr, s));
       }
       HIP_OK(cld_launch_route_vec((int)m, d->d_counters, d->d_requeue, s));
-      HIP_OK(cld_launch_order_long(V.offs, d->d_requeue, d->d_counters, d->d_lkey, d->d_lhist, d->d_lsorted, false, s));
-      HIP_OK(cld_launch_long_vec(d->d_T, V.in - base, V.offs, d->d_lsorted, V.out, d->d_slots, V.vslots, d->n_slots,
+      HIP_OK(cld_launch_order_long(ko, d->d_requeue, d->d_counters, d->d_lkey, d->d_lhist, d->d_lsorted, false, s));
+      HIP_OK(cld_launch_long_vec(d->d_T, kb, ko, d->d_lsorted, V.out, d->d_slots, V.vslots, d->n_slots,
                                  d->d_requeue2, d->d_counters, cflags & kCldFlags, sp ? V.sp : nullptr, pr ? V.pri : nullptr, hb, hf,
                                  hpz, hgz, V.pool, V.pool_off, V.nch, s));
+      if (chk) {
+        if (int rc = enqueue_fixup(d, V.out, m, s, V.nch)) return rc;
+      }
     }
     nch.resize(m);
     uint32_t ctr[kCtrSlots];
@@ -1847,6 +1930,7 @@ void cld_shutdown(void) {
     (void)hipFree(d->d_blob); (void)hipFree((void*)d->T.cpt); (void)hipFree((void*)d->T.keytab); (void)hipFree((void*)d->T.compat.adds); (void)hipFree(d->d_T); (void)hipFree(d->d_arena); (void)hipFree(d->d_counters);
     (void)hipFree(d->d_requeue); (void)hipFree(d->d_requeue2); (void)hipFree(d->d_lsorted); (void)hipFree(d->d_lkey); (void)hipFree(d->d_lhist); (void)hipFree(d->d_slots); (void)hipFree(d->d_buf); (void)hipFree(d->d_offs); (void)hipFree(d->d_out);
     (void)hipFree(d->d_sbuf); (void)hipFree(d->d_soffs); (void)hipFree(d->d_sscr);
+    (void)hipFree(d->d_vp); (void)hipFree(d->d_cbuf); (void)hipFree(d->d_coffs);
     (void)hipFree(d->d_hbuf); (void)hipFree(d->d_hflag); (void)hipFree(d->d_hpos);
     (void)hipFree(d->d_spec_out); (void)hipFree(d->d_spec_take);
     (void)hipFree(d->d_store); (void)hipFree(d->d_meta); (void)hipFree(d->d_stlists); (void)hipFree(d->d_parlists);
@@ -1855,6 +1939,7 @@ void cld_shutdown(void) {
       (void)hipHostFree(h.h_in); (void)hipHostFree(h.h_offs); (void)hipHostFree(h.h_out);
       (void)hipFree(h.d_in); (void)hipFree(h.d_offs); (void)hipFree(h.d_out);
       (void)hipHostFree(h.h_sp); (void)hipHostFree(h.h_pri); (void)hipFree(h.d_sp); (void)hipFree(h.d_pri);
+      (void)hipHostFree(h.h_vp); (void)hipFree(h.d_vp);
       (void)hipEventDestroy(h.up); (void)hipEventDestroy(h.comp); (void)hipEventDestroy(h.down);
     }
     (void)hipHostFree(d->h_ctr);
@@ -2171,11 +2256,22 @@ Device* pick_context() {
 }
 }  // namespace
 
+namespace {
+// The checked entries report positions as int32 (valid_prefix_bytes is an int
+// in the reference): no document may be longer than INT32_MAX.
+bool docs_fit_int32(const uint64_t* offsets, size_t n) {
+  uint64_t bad = 0;
+  for (size_t i = 0; i < n; ++i) bad |= (uint64_t)(offsets[i + 1] - offsets[i] > 0x7FFFFFFFull);
+  return bad == 0;
+}
+}  // namespace
+
 int cld_detect_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, cld_result* out, uint32_t flags) {
   if ((flags & ~(kPrepFlags | kPublicFlags)) != 0 || (n > 0 && (!buf || !offsets || !out))) return CLD_EINVAL;
   if (n == 0) return CLD_OK;
   if (n > 0x7FFFFFFFu) return CLD_EINVAL;
   if (!offsets_nondecreasing(offsets, n)) return CLD_EINVAL;
+  if ((flags & CLD_FLAG_CHECK_UTF8) && !docs_fit_int32(offsets, n)) return CLD_EINVAL;
   int rc = cld_init(nullptr, 0);
   if (rc) return rc;
   std::shared_lock<std::shared_mutex> tl(g_swap_mu);
@@ -2264,17 +2360,18 @@ int check_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, const voi
 }
 }  // namespace
 
-extern "C" {
-
-int cld_detect_batch_ex(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
-                        uint32_t flags, cld_result* out) {
-  if ((flags & ~(CLD_FLAG_HTML | kPublicFlags)) != 0) return CLD_EINVAL;
+// cld_detect_batch_ex, and with vp (n entries) cld_detect_batch_checked: the
+// valid prefixes of a CLD_FLAG_CHECK_UTF8 batch come back with the results.
+static int detect_batch_ex(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
+                           uint32_t flags, cld_result* out, int32_t* vp) {
+  if ((flags & ~(CLD_FLAG_HTML | CLD_FLAG_CHECK_UTF8 | kPublicFlags)) != 0) return CLD_EINVAL;
   if (int rc = check_batch(buf, offsets, n, out)) return rc;
   if (n == 0) return CLD_OK;
+  if ((flags & CLD_FLAG_CHECK_UTF8) && !docs_fit_int32(offsets, n)) return CLD_EINVAL;
   int rc = cld_init(nullptr, 0);
   if (rc) return rc;
   std::shared_lock<std::shared_mutex> tl(g_swap_mu);
-  const uint32_t cf = flags & kCldFlags;
+  const uint32_t cf = flags & (kCldFlags | CLD_FLAG_CHECK_UTF8);
   std::vector<uint8_t> special;
   std::vector<uint32_t> priors;
   const bool html = (flags & CLD_FLAG_HTML) != 0;
@@ -2282,10 +2379,10 @@ int cld_detect_batch_ex(const uint8_t* buf, const uint64_t* offsets, size_t n, c
   const uint8_t* sp = (html || !priors.empty()) ? special.data() : nullptr;
   const uint32_t* pr = priors.empty() ? nullptr : priors.data();
   const size_t ndev = g_devs.size();
-  if (ndev == 1) return run_host_shard_isolating(g_devs[0], buf, offsets, n, out, cf, sp, pr, html);
+  if (ndev == 1) return run_host_shard_isolating(g_devs[0], buf, offsets, n, out, cf, sp, pr, html, vp);
   if (offsets[n] - offsets[0] < small_batch_bytes()) {
     Picked p(pick_context());
-    return run_host_shard_isolating(p.d, buf, offsets, n, out, cf, sp, pr, html);
+    return run_host_shard_isolating(p.d, buf, offsets, n, out, cf, sp, pr, html, vp);
   }
   std::vector<size_t> cut(ndev + 1, 0);
   cld_plan_shards(offsets, n, (int)ndev, cut.data());
@@ -2296,20 +2393,95 @@ int cld_detect_batch_ex(const uint8_t* buf, const uint64_t* offsets, size_t n, c
     if (cut[k + 1] == cut[k]) continue;
     th.emplace_back([&, k] {
       rcs[k] = run_host_shard_isolating(g_devs[k], buf, offsets + cut[k], cut[k + 1] - cut[k], out + cut[k], cf,
-                              sp ? sp + cut[k] : nullptr, pr ? pr + 16 * cut[k] : nullptr, html);
+                              sp ? sp + cut[k] : nullptr, pr ? pr + 16 * cut[k] : nullptr, html,
+                              vp ? vp + cut[k] : nullptr);
     });
   }
   for (auto& t : th) t.join();
   return first_error(rcs);
 }
 
+extern "C" {
+
+int cld_detect_batch_ex(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
+                        uint32_t flags, cld_result* out) {
+  return detect_batch_ex(buf, offsets, n, hints, flags, out, nullptr);
+}
+
+// ExtDetectLanguageSummaryCheckUTF8 (compact_lang_det.cc:317-355) over a batch.
+int cld_detect_batch_checked(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
+                             uint32_t flags, cld_result* out, int32_t* valid_prefix) {
+  if ((flags & ~(CLD_FLAG_HTML | CLD_FLAG_CHECK_UTF8 | kPublicFlags)) != 0 || (n > 0 && !valid_prefix)) return CLD_EINVAL;
+  return detect_batch_ex(buf, offsets, n, hints, flags | CLD_FLAG_CHECK_UTF8, out, valid_prefix);
+}
+
+int32_t cld_valid_prefix_host(const uint8_t* doc, size_t len) {
+  if (len > 0x7FFFFFFFull || (len > 0 && !doc)) return CLD_EINVAL;
+  uint32_t l1 = 0, l2 = 0, l3 = 0;              // char_len at p-1, p-2, p-3
+  for (size_t p = 0; p < len; ++p) {
+    const uint32_t c = doc[p], n1 = p + 1 < len ? doc[p + 1] : 0, n2 = p + 2 < len ? doc[p + 2] : 0,
+                   n3 = p + 3 < len ? doc[p + 3] : 0;
+    const uint32_t l0 = cld::valid::char_len(c, n1, n2, n3);
+    if (cld::valid::is_error(c, l0, l1, l2, l3)) return (int32_t)p;
+    l3 = l2; l2 = l1; l1 = l0;
+  }
+  return (int32_t)len;
+}
+
+int cld_valid_prefix_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                            int32_t* d_valid_prefix, void* stream) {
+  if (n > 0x7FFFFFFFu || (n > 0 && (!d_buf || !d_offsets || !d_valid_prefix))) return CLD_EINVAL;
+  int rc = cld_init(nullptr, 0);
+  if (rc) return rc;
+  if (device < 0 || device >= (int)g_devs.size()) return CLD_EINVAL;
+  if (n == 0) return CLD_OK;
+  Device* d = g_devs[device];
+  HIP_OK(hipSetDevice(d->id));
+  // (no scratch of the context is used: nothing to serialise with other batches)
+  HIP_OK(cld_launch_valid_prefix(d_buf, d_offsets, (int)n, d_valid_prefix, 0, stream ? (hipStream_t)stream : d->stream));
+  return CLD_OK;
+}
+
+int cld_valid_prefix_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, int32_t* valid_prefix) {
+  if (n > 0 && (!buf || !offsets || !valid_prefix)) return CLD_EINVAL;
+  if (n == 0) return CLD_OK;
+  if (n > 0x7FFFFFFFu || !offsets_nondecreasing(offsets, n) || !docs_fit_int32(offsets, n)) return CLD_EINVAL;
+  int rc = cld_init(nullptr, 0);
+  if (rc) return rc;
+  Device* d = g_devs[0];
+  std::lock_guard<std::mutex> lk(d->mu);
+  HIP_OK(hipSetDevice(d->id));
+  HIP_OK(hipStreamWaitEvent(d->stream, d->done, 0));   // an earlier batch may still use d_vp
+  // pieces of at most 256 MB of text / 4M documents (one document at least)
+  constexpr uint64_t kPieceBytes = 256ull << 20;
+  constexpr size_t kPieceDocs = 4u << 20;
+  for (size_t a = 0; a < n;) {
+    size_t m = 1;
+    while (a + m < n && m < kPieceDocs && offsets[a + m + 1] - offsets[a] <= kPieceBytes) ++m;
+    const uint64_t base = offsets[a], bytes = offsets[a + m] - base;
+    if (grow(&d->d_buf, &d->buf_cap, std::max<size_t>(bytes, 1))) return CLD_ENOMEM;
+    if (grow(&d->d_offs, &d->offs_cap, m + 1)) return CLD_ENOMEM;
+    if (grow(&d->d_vp, &d->vp_cap, m)) return CLD_ENOMEM;
+    if (bytes) HIP_OK(hipMemcpyAsync(d->d_buf, buf + base, bytes, hipMemcpyHostToDevice, d->stream));
+    HIP_OK(hipMemcpyAsync(d->d_offs, offsets + a, (m + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, d->stream));
+    // (the offsets go up as the caller wrote them: the buffer base is biased instead)
+    HIP_OK(cld_launch_valid_prefix(d->d_buf - base, d->d_offs, (int)m, d->d_vp, bytes, d->stream));
+    HIP_OK(hipMemcpyAsync(valid_prefix + a, d->d_vp, m * sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
+    HIP_OK(hipStreamSynchronize(d->stream));
+    a += m;
+  }
+  return CLD_OK;
+}
+
 int cld_detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
                          uint32_t flags, cld_result* out, cld_chunk* chunks, size_t chunk_cap,
                          uint64_t* chunk_offsets) {
-  if ((flags & ~(CLD_FLAG_HTML | kPublicFlags)) != 0 || !chunk_offsets || (chunk_cap > 0 && !chunks)) return CLD_EINVAL;
+  if ((flags & ~(CLD_FLAG_HTML | CLD_FLAG_CHECK_UTF8 | kPublicFlags)) != 0 || !chunk_offsets || (chunk_cap > 0 && !chunks))
+    return CLD_EINVAL;
   if (int rc = check_batch(buf, offsets, n, out)) return rc;
   chunk_offsets[0] = 0;
   if (n == 0) return CLD_OK;
+  if ((flags & CLD_FLAG_CHECK_UTF8) && !docs_fit_int32(offsets, n)) return CLD_EINVAL;
   int rc = cld_init(nullptr, 0);
   if (rc) return rc;
   std::shared_lock<std::shared_mutex> tl(g_swap_mu);
@@ -2332,7 +2504,7 @@ int cld_detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t n, 
     auto job = [&, k] {
       rcs[k] = run_vec_shard(g_devs[k], buf, offsets + cut[k], cut[k + 1] - cut[k], out + cut[k],
                              sp ? sp + cut[k] : nullptr, pr ? pr + 16 * cut[k] : nullptr, &vs[k], &cs[k],
-                             flags & kCldFlags);
+                             flags & (kCldFlags | CLD_FLAG_CHECK_UTF8));
     };
     if (ndev == 1) job(); else th.emplace_back(job);
   }
@@ -2383,12 +2555,13 @@ int cld_detect_batch_device_ex(int device, const uint8_t* d_buf, const uint64_t*
   if (d->ev_used >= 4096) d->ev_used = 0;
   if (!(flags & kPrepFlags)) return enqueue(d, d_buf, d_offsets, n, d_out, s, nullptr, nullptr, flags);
   if ((rc = enqueue_prepare(d, d_buf, d_offsets, n, buf_bytes, flags, s))) return rc;
-  return enqueue(d, d->d_sbuf, d->d_soffs, n, d_out, s, nullptr, nullptr, flags);
+  if ((rc = enqueue(d, d->p_buf, d->p_offs, n, d_out, s, nullptr, nullptr, flags))) return rc;
+  return (flags & CLD_FLAG_CHECK_UTF8) ? enqueue_fixup(d, d_out, n, s) : CLD_OK;
 }
 
 int cld_prepare_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, uint32_t flags,
                       uint8_t* out_buf, uint64_t* out_offsets) {
-  if ((flags & ~kPrepFlags) != 0 || !offsets || !out_offsets || (n > 0 && (!buf || !out_buf))) return CLD_EINVAL;
+  if ((flags & ~kStripFlags) != 0 || !offsets || !out_offsets || (n > 0 && (!buf || !out_buf))) return CLD_EINVAL;
   if (n > 0x7FFFFFFFu) return CLD_EINVAL;
   if (!offsets_nondecreasing(offsets, n)) return CLD_EINVAL;
   if (n == 0) { out_offsets[0] = 0; return CLD_OK; }
@@ -2578,6 +2751,18 @@ const char* detect_language(const char* text) {
   if (lang == (int)g_tab.meta.unknown_language) lang = (int)g_tab.meta.english;  // compact_lang_det.cc:91-93
   if (lang < 0 || (size_t)lang >= g_tab.codes.size()) lang = (int)g_tab.meta.unknown_language;
   return (size_t)lang < g_tab.codes.size() ? g_tab.codes[lang] : "un";
+}
+
+// DetectLanguageCheckUTF8 (compact_lang_det.cc:44-56): the check on the host
+// (a request text is short), then detect_language.  A rejected text never
+// reaches the per-call queue.
+const char* detect_language_checked(const char* text, int* valid_prefix_bytes) {
+  const char* t = text ? text : "";
+  const size_t len = strlen(t);
+  const int32_t vp = cld_valid_prefix_host((const uint8_t*)t, len);
+  if (valid_prefix_bytes) *valid_prefix_bytes = vp;
+  if (vp < 0 || (size_t)vp < len) return cld_language_code(26);   // UNKNOWN_LANGUAGE, not mapped to English there
+  return detect_language(t);
 }
 
 }  // extern "C"

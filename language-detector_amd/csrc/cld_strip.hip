@@ -222,6 +222,19 @@ hipError_t cld_launch_strip_offsets(const uint8_t* buf, const uint64_t* offs, in
   return hipGetLastError();
 }
 
+// The scan alone: the caller has written the n lengths to scratch[0..n).
+hipError_t cld_launch_scan_lengths(int n, uint64_t* out_offs, void* scratch, hipStream_t s) {
+  using namespace cld::strip;
+  if (n <= 0) return hipMemsetAsync(out_offs, 0, sizeof(uint64_t), s);
+  uint64_t* len = (uint64_t*)scratch;
+  uint64_t* tile = len + n;
+  const int ntiles = (n + kScanBlock - 1) / kScanBlock;
+  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(kScanBlock), 0, s, len, n, out_offs, tile);
+  hipLaunchKernelGGL(k_scan_carry, dim3(1), dim3(kScanBlock), 0, s, tile, ntiles);
+  hipLaunchKernelGGL(k_scan_add, dim3(ntiles), dim3(kScanBlock), 0, s, out_offs, n, tile);
+  return hipGetLastError();
+}
+
 hipError_t cld_launch_strip_write(const uint8_t* buf, const uint64_t* offs, int n, uint32_t flags,
                                   const uint64_t* out_offs, uint8_t* out, hipStream_t s) {
   using namespace cld::strip;
