@@ -1,7 +1,7 @@
 // cld_runtime.cpp -- host runtime behind the C ABI (include/cld_mi355x.h).
 //
 //  * loads the CLDT table blob once per process, uploads it once per GPU;
-//  * one context per GPU: stream, table copy, general-kernel arena, staging;
+//  * one context per GPU: streams, table copy, scratch and staging (cld_owned.h);
 //  * cld_detect_batch shards documents across GPUs by byte count (documents
 //    are independent: no collective on the hot path), one host thread per GPU;
 //  * detect_language() (wrapper.h:8) coalesces concurrent callers into GPU
@@ -32,10 +32,25 @@
 #include "cld_dynamic_data.h"
 #include "cld_hints.h"
 #include "cld_kernels.h"
+#include "cld_owned.h"
 #include "cld_valid_rule.h"
 #include "cldt_format.h"
 
 namespace {
+
+template <class T> using DevBuf = cld::Buf<T, cld::Mem::Device>;
+template <class T> using PinBuf = cld::Buf<T, cld::Mem::Pinned>;
+
+// Environment knobs: the default when unset, else what atol / strtoull make
+// of the value (text that is no number parses to 0).
+long env_long(const char* name, long dflt) {
+  const char* e = getenv(name);
+  return e ? atol(e) : dflt;
+}
+uint64_t env_u64(const char* name, uint64_t dflt) {
+  const char* e = getenv(name);
+  return e ? strtoull(e, nullptr, 10) : dflt;
+}
 
 // Inside a loop that has enqueued DMA on the caller's buffers: record the
 // error and leave the loop, so the drain after it still runs.
@@ -64,6 +79,29 @@ bool offsets_nondecreasing(const uint64_t* offsets, size_t n) {
   uint64_t bad = 0;
   for (size_t i = 0; i < n; ++i) bad |= (uint64_t)(offsets[i + 1] < offsets[i]);
   return bad == 0;
+}
+
+// every document short enough for k_wave (branch-free for the same reason)
+bool all_fit_wave(const uint64_t* offs, size_t n) {
+  uint64_t bad = 0;
+  for (size_t i = 0; i < n; ++i) bad |= (uint64_t)(offs[i + 1] - offs[i] > (uint64_t)kWaveCap);
+  return bad == 0;
+}
+
+// The checked entries report positions as int32 (valid_prefix_bytes is an int
+// in the reference): no document may be longer than INT32_MAX.
+bool docs_fit_int32(const uint64_t* offsets, size_t n) {
+  uint64_t bad = 0;
+  for (size_t i = 0; i < n; ++i) bad |= (uint64_t)(offsets[i + 1] - offsets[i] > 0x7FFFFFFFull);
+  return bad == 0;
+}
+
+// The argument checks every host batch entry point shares.
+int check_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, const void* out) {
+  if (n > 0 && (!buf || !offsets || !out)) return CLD_EINVAL;
+  if (n > 0x7FFFFFFFu) return CLD_EINVAL;
+  if (!offsets_nondecreasing(offsets, n)) return CLD_EINVAL;
+  return CLD_OK;
 }
 
 // ------------------------------------------------------------ host tables
@@ -361,30 +399,39 @@ constexpr size_t kTinyOffsOff = kTinyCtrOff + kCtrSlots * sizeof(uint32_t);
 constexpr size_t kTinyBlock = kTinyOffsOff + (kTinyDocs + 1) * sizeof(uint64_t) + kTinyDocs * kWaveCap + 256;
 constexpr int kTinySlotsMax = 4;   // calls in flight per context (each its own stream); CLD_TINY_SLOTS, default 4
 int tiny_slots() {
-  static const int v = getenv("CLD_TINY_SLOTS") ? std::max(1, std::min(kTinySlotsMax, atoi(getenv("CLD_TINY_SLOTS")))) : 4;
+  static const int v = std::max(1, std::min(kTinySlotsMax, (int)env_long("CLD_TINY_SLOTS", 4)));
   return v;
 }
 struct TinySlot {
-  hipStream_t s = nullptr;
-  uint8_t* h = nullptr;          // pinned
+  cld::Stream s;
+  PinBuf<uint8_t> h;             // pinned
   uint8_t* hd = nullptr;         // the pinned block's device address (zero-copy mode)
-  uint8_t* dv = nullptr;         // device
-  uint32_t* d_rq = nullptr;      // k_wave's re-queue list
+  DevBuf<uint8_t> dv;            // device
   std::mutex mu;
 };
 
+// Every member that owns something releases it itself (cld_owned.h), the
+// tables through ~Device.  Streams and events are declared before the buffers
+// of their struct: members go in reverse order, so buffers are freed before
+// the streams and events that worked on them are destroyed.
 struct Device {
   int id = 0;
-  hipStream_t stream = nullptr;
-  uint8_t* d_blob = nullptr;
+  cld::Stream stream;
+  cld::Stream up_stream, down_stream;   // the streamed host path's copies (run_host_stream)
+  // Every batch on this device reuses the scratch below (counters, re-queue
+  // lists, k_long slots, staging).  `done` is recorded after a batch's last
+  // launch and every enqueue makes its stream wait on it first, so batches on
+  // different caller streams (or the runtime's own) execute one after another.
+  cld::Event done;
+  hipEvent_t ev[4]{};                               // the last enqueue's set (owned by ev_pool)
+  std::deque<std::array<cld::Event, 4>> ev_pool;    // one set per enqueue since reset
+  size_t ev_used = 0;
+  uint8_t* d_blob = nullptr;  // the table blob and T.cpt / keytab / compat.adds: commit_tables, drop_tables
   DevTables T{};
-  DevTables* d_T = nullptr;   // T in HBM (k_long reads the table set through a pointer)
-  uint8_t* d_arena = nullptr;
-  uint64_t stride = 0;
-  int lanes = 0;
-  uint8_t* d_slots = nullptr; // k_long per-wave slots 
-  cld_result* d_spec_out = nullptr;   // k_long's speculative pass-2 results (small batches; CLD_LONG_SPEC=0: off)
-  uint32_t* d_spec_take = nullptr;
+  DevBuf<DevTables> d_T;      // T in HBM (k_long reads the table set through a pointer)
+  DevBuf<uint8_t> d_slots;    // k_long per-wave slots
+  DevBuf<cld_result> d_spec_out;   // k_long's speculative pass-2 results (small batches; CLD_LONG_SPEC=0: off)
+  DevBuf<uint32_t> d_spec_take;
   int n_slots = 0;               // the fused k_long's resident waves (its grid)
   // Staged long-document path (cld_launch_staged; CLD_LONG_STAGED=0: off):
   // pass 1's spans of every long document in a store (CLD_LONG_STORE_MB, 8 GB
@@ -392,99 +439,88 @@ struct Device {
   // entries' regions (meta) and the stage lists
   bool staged = false;
   int st_waves = 0;             // slots the staged kernels use (>= n_slots slots are allocated)
-  uint8_t* d_store = nullptr; uint64_t store_bytes = 0;
-  uint64_t* d_meta = nullptr; size_t meta_cap = 0;
-  uint32_t* d_stlists = nullptr; size_t stlists_cap = 0;   // ok / pass-2 / fallback lists, 3 x cap
-  uint32_t* d_parlists = nullptr; size_t parlists_cap = 0; // span-parallel: 2 document lists + 2 group lists
-  uint32_t* d_requeue2 = nullptr;
-  size_t requeue2_cap = 0;
+  DevBuf<uint8_t> d_store; uint64_t store_bytes = 0;
+  DevBuf<uint64_t> d_meta;
+  DevBuf<uint32_t> d_stlists;   // ok / pass-2 / fallback lists, 3 x cap
+  DevBuf<uint32_t> d_parlists;  // span-parallel: 2 document lists + 2 group lists
+  DevBuf<uint32_t> d_requeue2;
   bool long_order = true;       // k_long takes its list longest first (CLD_LONG_ORDER=0: arrival order)
-  uint32_t* d_lsorted = nullptr; size_t lsorted_cap = 0;   // k_long list, longest first
-  uint8_t* d_lkey = nullptr; size_t lkey_cap = 0;          // length bucket per re-queued document
-  uint32_t* d_lhist = nullptr;                             // bucket histogram + scatter cursors
-  uint32_t* h_trace = nullptr;  // CLD_TRACE=1: pinned host progress words, 4 per k_long wave
-  uint32_t* d_dbg = nullptr;    // CLD_DEBUG_DOC=i: k_long dumps document i's rounds/chunks
+  DevBuf<uint32_t> d_lsorted;   // k_long list, longest first
+  DevBuf<uint8_t> d_lkey;       // length bucket per re-queued document
+  DevBuf<uint32_t> d_lhist;     // bucket histogram + scatter cursors
+  cld::Buf<uint32_t, cld::Mem::PinnedMapped> h_trace;   // CLD_TRACE=1: pinned host progress words, 4 per k_long wave
+  DevBuf<uint32_t> d_dbg;       // CLD_DEBUG_DOC=i: k_long dumps document i's rounds/chunks
   uint32_t dbg_doc = 0xFFFFFFFFu;
   uint32_t fault_doc = 0xFFFFFFFFu;   // CLD_FAULT_DOC=i (tests): batch document i gets no result in k_long
   double trace_timeout = 0;
-  unsigned long long* d_prof = nullptr;   // per-stage cycle sums (CLD_PROFILE_STAGES=1)
-  uint32_t* d_counters = nullptr;
-  uint32_t* d_requeue = nullptr;
-  size_t requeue_cap = 0;
-  uint8_t* d_buf = nullptr; size_t buf_cap = 0;
-  uint64_t* d_offs = nullptr; size_t offs_cap = 0;
-  cld_result* d_out = nullptr; size_t out_cap = 0;
-  uint8_t* d_sbuf = nullptr; size_t sbuf_cap = 0;        // prepared text (CLD_FLAG_STRIP_EXTRAS / CSTRING)
-  uint8_t* d_hbuf = nullptr; size_t hbuf_cap = 0;        // HTML pages rewritten into plain text (cld_html.hip)
-  uint8_t* d_hflag = nullptr; size_t hflag_cap = 0;      //   and their entity lookahead marks
-  uint32_t* d_hpos = nullptr; size_t hpos_cap = 0;       //   and (vec mode) each byte's page offset
-  uint64_t* d_soffs = nullptr; size_t soffs_cap = 0;
-  uint8_t* d_sscr = nullptr; size_t sscr_cap = 0;
+  DevBuf<unsigned long long> d_prof;   // per-stage cycle sums (CLD_PROFILE_STAGES=1)
+  // the fused kernel's diagnostics (trace / debug dump / stage cycles): such batches skip the staged path;
+  // any diagnostic, fault injection included: no tiny path, no per-call queue
+  bool fused_diagnostics() const { return h_trace || d_dbg || d_prof; }
+  bool diagnostics() const { return fused_diagnostics() || fault_doc != 0xFFFFFFFFu; }
+  DevBuf<uint32_t> d_counters;
+  DevBuf<uint32_t> d_requeue;
+  DevBuf<uint8_t> d_buf;        // cld_prepare_batch / cld_valid_prefix_batch: the uploaded batch
+  DevBuf<uint64_t> d_offs;
+  DevBuf<uint8_t> d_sbuf;       // prepared text (CLD_FLAG_STRIP_EXTRAS / CSTRING)
+  DevBuf<uint8_t> d_hbuf;       // HTML pages rewritten into plain text (cld_html.hip)
+  DevBuf<uint8_t> d_hflag;      //   and their entity lookahead marks
+  DevBuf<uint32_t> d_hpos;      //   and (vec mode) each byte's page offset
+  DevBuf<uint64_t> d_soffs;
+  DevBuf<uint8_t> d_sscr;
   // CLD_FLAG_CHECK_UTF8 (cld_valid.hip): valid prefixes, and the prepared batch in which a rejected
   // document is empty.  p_buf / p_offs: where enqueue_prepare left the prepared batch (d_sbuf or d_cbuf);
   // chk_offs / chk_vp: the offsets and prefixes the check ran on (enqueue_fixup reads them)
-  int32_t* d_vp = nullptr; size_t vp_cap = 0;
-  uint8_t* d_cbuf = nullptr; size_t cbuf_cap = 0;
-  uint64_t* d_coffs = nullptr; size_t coffs_cap = 0;
+  DevBuf<int32_t> d_vp;
+  DevBuf<uint8_t> d_cbuf;
+  DevBuf<uint64_t> d_coffs;
   const uint8_t* p_buf = nullptr; const uint64_t* p_offs = nullptr;
   const uint64_t* chk_offs = nullptr; const int32_t* chk_vp = nullptr;
-  hipEvent_t ev[4]{};
-  std::vector<std::array<hipEvent_t, 4>> ev_pool;   // one set per enqueue since reset
-  size_t ev_used = 0;
   cld_batch_stats last{};
   uint64_t last_n = 0;
   bool stats_pending = false;
-  // Every batch on this device reuses the scratch above (counters, re-queue
-  // lists, k_long slots, staging).  `done` is recorded after a batch's last
-  // launch and every enqueue makes its stream wait on it first, so batches on
-  // different caller streams (or the runtime's own) execute one after another.
-  hipEvent_t done = nullptr;
   // Streamed host path (run_host_shard): two chunk slots, each with pinned
   // staging and device buffers; uploads, kernels and downloads on three
   // streams so chunk k+1's upload and chunk k-1's download overlap chunk k.
   struct Slot {
-    uint8_t* h_in = nullptr; size_t h_in_cap = 0;        // pinned: document bytes
-    uint64_t* h_offs = nullptr; size_t h_offs_cap = 0;   // pinned: offsets (caller's, not rebased)
-    cld_result* h_out = nullptr; size_t h_out_cap = 0;   // pinned: results
-    uint8_t* d_in = nullptr; size_t d_in_cap = 0;
-    uint64_t* d_offs = nullptr; size_t d_offs_cap = 0;
-    cld_result* d_out = nullptr; size_t d_out_cap = 0;
-    uint8_t* h_sp = nullptr; size_t h_sp_cap = 0;        // cld_detect_batch_ex: routing bits + priors
-    uint32_t* h_pri = nullptr; size_t h_pri_cap = 0;
-    uint8_t* d_sp = nullptr; size_t d_sp_cap = 0;
-    uint32_t* d_pri = nullptr; size_t d_pri_cap = 0;
-    int32_t* d_vp = nullptr; size_t d_vp_cap = 0;        // CLD_FLAG_CHECK_UTF8: the chunk's valid prefixes
-    int32_t* h_vp = nullptr; size_t h_vp_cap = 0;        //   and their pinned copy (cld_detect_batch_checked)
-    hipEvent_t up = nullptr, comp = nullptr, down = nullptr;
+    cld::Event up, comp, down;
+    PinBuf<uint8_t> h_in;         // pinned: document bytes
+    PinBuf<uint64_t> h_offs;      // pinned: offsets (caller's, not rebased)
+    PinBuf<cld_result> h_out;     // pinned: results
+    DevBuf<uint8_t> d_in;
+    DevBuf<uint64_t> d_offs;
+    DevBuf<cld_result> d_out;
+    PinBuf<uint8_t> h_sp;         // cld_detect_batch_ex: routing bits + priors
+    PinBuf<uint32_t> h_pri;
+    DevBuf<uint8_t> d_sp;
+    DevBuf<uint32_t> d_pri;
+    DevBuf<int32_t> d_vp;         // CLD_FLAG_CHECK_UTF8: the chunk's valid prefixes
+    PinBuf<int32_t> h_vp;         //   and their pinned copy (cld_detect_batch_checked)
     size_t pending_n = 0; cld_result* pending_dst = nullptr;   // results to hand over once `down` fires
     int32_t* pending_vp = nullptr;
     bool busy = false;
   } hs[2];
-  hipStream_t up_stream = nullptr, down_stream = nullptr;
-  uint32_t* h_ctr = nullptr;        // pinned: per-chunk counter snapshots (kCtrSlots each)
-  size_t h_ctr_cap = 0;
-  uint32_t* d_ctrs = nullptr;       // device: per-chunk counters of one streamed call (kCtrSlots each)
-  size_t ctrs_cap = 0;
-  // ResultChunkVector mode (cld_detect_batch_vec): its own lane arena, made on first use
+  PinBuf<uint32_t> h_ctr;       // pinned: per-chunk counter snapshots (kCtrSlots each)
+  DevBuf<uint32_t> d_ctrs;      // device: per-chunk counters of one streamed call (kCtrSlots each)
+  // ResultChunkVector mode (cld_detect_batch_vec): its buffers, made on first use
   struct Vec {
-    uint8_t* arena = nullptr; uint64_t stride = 0; int lanes = 0;
-    uint8_t* in = nullptr; size_t in_cap = 0;
-    uint64_t* offs = nullptr; size_t offs_cap = 0;
-    cld_result* out = nullptr; size_t out_cap = 0;
-    uint8_t* sp = nullptr; size_t sp_cap = 0;
-    uint32_t* pri = nullptr; size_t pri_cap = 0;
-    cld_chunk* pool = nullptr; size_t pool_cap = 0;
-    uint64_t* pool_off = nullptr; size_t pool_off_cap = 0;
-    int32_t* nch = nullptr; size_t nch_cap = 0;
-    uint64_t* pos = nullptr; size_t pos_cap = 0;
-    uint32_t* order = nullptr; size_t order_cap = 0;
-    cld_chunk* compact = nullptr; size_t compact_cap = 0;
-    uint8_t* vslots = nullptr;   // k_long<VEC>: one VecSlot per slot of d_slots (on first use)
+    DevBuf<uint8_t> in;
+    DevBuf<uint64_t> offs;
+    DevBuf<cld_result> out;
+    DevBuf<uint8_t> sp;
+    DevBuf<uint32_t> pri;
+    DevBuf<cld_chunk> pool;
+    DevBuf<uint64_t> pool_off;
+    DevBuf<int32_t> nch;
+    DevBuf<uint64_t> pos;
+    DevBuf<cld_chunk> compact;
+    DevBuf<uint8_t> vslots;   // k_long<VEC>: one VecSlot per slot of d_slots (on first use)
   } vec;
   TinySlot tiny[kTinySlotsMax];   // run_tiny: k_wave-only calls, independent of the scratch above (tiny_slots() used)
   std::atomic<unsigned> tiny_rr{0};
   std::mutex mu;
   std::atomic<int> inflight{0};   // calls routed to this context and not yet returned (pick_context)
+  ~Device();
 };
 
 std::mutex g_init_mu;
@@ -515,17 +551,6 @@ std::string default_tables_path() {
     return dir + "/../data/cld2_q0.cldt";
   }
   return "language-detector_amd/data/cld2_q0.cldt";
-}
-
-template <class T>
-int grow(T** p, size_t* cap, size_t need) {
-  if (*cap >= need) return CLD_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  size_t n = std::max(need, *cap * 3 / 2);
-  if (hipMalloc((void**)p, n * sizeof(T)) != hipSuccess) { *cap = 0; return CLD_ENOMEM; }
-  *cap = n;
-  return CLD_OK;
 }
 
 // Table blob -> HBM (once per GPU, and again when dynamic data replaces the
@@ -567,20 +592,38 @@ void discard_tables(Device* d, StagedTables* st) {
   *st = StagedTables();
 }
 
-// The caller holds d->mu or owns d exclusively.
-int commit_tables(Device* d, StagedTables* st) {
-  HIP_OK(hipSetDevice(d->id));
-  HIP_OK(hipDeviceSynchronize());   // batches enqueued on caller streams may still read the old blob
+// Frees the device's live table copy (nothing on the device reads it any more).
+void drop_tables(Device* d) {
   if (d->d_blob) (void)hipFree(d->d_blob);
   if (d->T.cpt) (void)hipFree((void*)d->T.cpt);
   if (d->T.keytab) (void)hipFree((void*)d->T.keytab);
   if (d->T.compat.adds) (void)hipFree((void*)d->T.compat.adds);
+  d->d_blob = nullptr;
+  d->T = DevTables{};
+}
+
+// The caller holds d->mu or owns d exclusively.
+int commit_tables(Device* d, StagedTables* st) {
+  HIP_OK(hipSetDevice(d->id));
+  HIP_OK(hipDeviceSynchronize());   // batches enqueued on caller streams may still read the old blob
+  drop_tables(d);
   d->d_blob = st->blob;
   d->T = st->T;
   *st = StagedTables();
-  if (!d->d_T) HIP_OK(hipMalloc(&d->d_T, sizeof(DevTables)));
+  if (d->d_T.reserve(1)) return CLD_EFAULT;
   HIP_OK(hipMemcpy(d->d_T, &d->T, sizeof(DevTables), hipMemcpyHostToDevice));
   return CLD_OK;
+}
+
+// cld_shutdown deletes the contexts (no call is in flight).  The streams are
+// drained here; then the members free the buffers and, after those, destroy
+// the events and streams (declaration order, see Device).
+Device::~Device() {
+  (void)hipSetDevice(id);
+  if (stream) (void)hipStreamSynchronize(stream);
+  for (TinySlot& t : tiny)
+    if (t.s) (void)hipStreamSynchronize(t.s);
+  drop_tables(this);
 }
 
 int upload_tables(Device* d, const HostTables& t) {
@@ -591,7 +634,25 @@ int upload_tables(Device* d, const HostTables& t) {
 }
 
 // Replace the tables on every initialised GPU, or on none.  Caller holds g_init_mu.
-int swap_tables_all(const HostTables& nt);
+int swap_tables_all(const HostTables& nt) {
+  std::vector<StagedTables> st(g_devs.size());
+  for (size_t i = 0; i < g_devs.size(); ++i) {
+    std::lock_guard<std::mutex> dl(g_devs[i]->mu);
+    if (int rc = stage_tables(g_devs[i], nt, &st[i])) {
+      for (size_t j = 0; j <= i; ++j) discard_tables(g_devs[j], &st[j]);
+      fprintf(stderr, "cld_mi355x: table upload failed on device %d; the tables in use are kept\n", g_devs[i]->id);
+      return rc;
+    }
+  }
+  for (size_t i = 0; i < g_devs.size(); ++i) {       // cannot fail short of a device error
+    std::lock_guard<std::mutex> dl(g_devs[i]->mu);
+    if (int rc = commit_tables(g_devs[i], &st[i])) return rc;
+  }
+  return CLD_OK;
+}
+
+// A fixed-size allocation of init_device: failing it is a device error like any HIP call failing there.
+#define ALLOC_OK(buf, n) HIP_OK((buf).reserve(n) == CLD_OK ? hipSuccess : hipErrorOutOfMemory)
 
 int init_device(Device* d) {
   HIP_OK(hipSetDevice(d->id));
@@ -605,86 +666,75 @@ int init_device(Device* d) {
     (void)hipSetDeviceFlags(f);
     (void)hipGetLastError();
   }
-  HIP_OK(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-  HIP_OK(hipStreamCreateWithFlags(&d->up_stream, hipStreamNonBlocking));
-  HIP_OK(hipStreamCreateWithFlags(&d->down_stream, hipStreamNonBlocking));
-  HIP_OK(hipEventCreateWithFlags(&d->done, hipEventDisableTiming));
+  for (cld::Stream* q : {&d->stream, &d->up_stream, &d->down_stream})
+    HIP_OK(hipStreamCreateWithFlags(&q->h, hipStreamNonBlocking));
+  HIP_OK(hipEventCreateWithFlags(&d->done.h, hipEventDisableTiming));
   HIP_OK(hipEventRecord(d->done, d->stream));
-  for (auto& h : d->hs) {
-    HIP_OK(hipEventCreateWithFlags(&h.up, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&h.comp, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&h.down, hipEventDisableTiming));
-  }
+  for (auto& h : d->hs)
+    for (cld::Event* e : {&h.up, &h.comp, &h.down}) HIP_OK(hipEventCreateWithFlags(&e->h, hipEventDisableTiming));
   if (int rc = upload_tables(d, g_tab)) return rc;
   for (int k = 0; k < tiny_slots(); ++k) {
     TinySlot& t = d->tiny[k];
-    HIP_OK(hipStreamCreateWithFlags(&t.s, hipStreamNonBlocking));
-    HIP_OK(hipHostMalloc((void**)&t.h, kTinyBlock, hipHostMallocDefault));
+    HIP_OK(hipStreamCreateWithFlags(&t.s.h, hipStreamNonBlocking));
+    ALLOC_OK(t.h, kTinyBlock);
     HIP_OK(hipHostGetDevicePointer((void**)&t.hd, t.h, 0));
-    HIP_OK(hipMalloc(&t.dv, kTinyBlock));
-    HIP_OK(hipMalloc(&t.d_rq, kTinyDocs * sizeof(uint32_t)));
+    ALLOC_OK(t.dv, kTinyBlock);
   }
-  HIP_OK(hipMalloc(&d->d_counters, kCtrSlots * sizeof(uint32_t)));
-  HIP_OK(hipMalloc(&d->d_lhist, 256 * sizeof(uint32_t)));
-  if (const char* e = getenv("CLD_LONG_ORDER")) d->long_order = atoi(e) != 0;
+  ALLOC_OK(d->d_counters, kCtrSlots);
+  ALLOC_OK(d->d_lhist, 256);
+  d->long_order = env_long("CLD_LONG_ORDER", 1) != 0;
   hipDeviceProp_t prop;
   HIP_OK(hipGetDeviceProperties(&prop, d->id));
-  if (const char* e = getenv("CLD_PROFILE_STAGES")) {
-    if (atoi(e) > 0) {
-      HIP_OK(hipMalloc(&d->d_prof, 16 * sizeof(unsigned long long)));
-      HIP_OK(hipMemset(d->d_prof, 0, 16 * sizeof(unsigned long long)));
-    }
+  if (env_long("CLD_PROFILE_STAGES", 0) > 0) {
+    ALLOC_OK(d->d_prof, 16);
+    HIP_OK(hipMemset(d->d_prof, 0, 16 * sizeof(unsigned long long)));
   }
   // k_long: one slot per resident wavefront of its persistent grid; every
   // document longer than k_wave takes, or that k_wave hands on, runs there
-  int waves = 4 * cld_long_waves_per_simd();   // fill every SIMD at the kernel's occupancy
-  if (const char* e = getenv("CLD_LONG_WAVES")) waves = std::max(1, atoi(e));
+  // (CLD_LONG_WAVES overrides the default, which fills every SIMD at the kernel's occupancy)
+  const int waves = std::max(1, (int)env_long("CLD_LONG_WAVES", 4 * cld_long_waves_per_simd()));
   int n_slots = (prop.multiProcessorCount * waves / kLongWPB) * kLongWPB;
   const uint64_t slot = cld_long_slot_bytes();
   while (n_slots > kLongWPB && (uint64_t)n_slots * slot > (8ull << 30)) n_slots -= kLongWPB;
   if (n_slots < kLongWPB) return CLD_ENOMEM;
   int alloc_slots = n_slots;
-  if (n_slots > 0 && !(getenv("CLD_LONG_STAGED") && atoi(getenv("CLD_LONG_STAGED")) == 0)) {
+  if (n_slots > 0 && env_long("CLD_LONG_STAGED", 1) != 0) {
     const int st = prop.multiProcessorCount * 4 * cld_staged_waves_per_simd();
-    uint64_t mb = 8192;
-    if (const char* e = getenv("CLD_LONG_STORE_MB")) mb = strtoull(e, nullptr, 10);
+    const uint64_t mb = env_u64("CLD_LONG_STORE_MB", 8192);
     // (64 KB past the last region: the span readers' slack reads stay inside the allocation)
-    if (mb && (uint64_t)st * slot <= (12ull << 30) && hipMalloc(&d->d_store, (mb << 20) + (64u << 10)) == hipSuccess) {
+    if (mb && (uint64_t)st * slot <= (12ull << 30) && d->d_store.reserve((mb << 20) + (64u << 10)) == CLD_OK) {
       d->store_bytes = mb << 20;
       d->st_waves = st;
       d->staged = true;
       alloc_slots = std::max(n_slots, st);
     } else {
-      (void)hipGetLastError();
-      d->d_store = nullptr;
+      (void)hipGetLastError();   // (no store: every long document takes the fused kernel)
     }
   }
   if (n_slots > 0) {
-    HIP_OK(hipMalloc(&d->d_slots, (uint64_t)alloc_slots * slot));
+    ALLOC_OK(d->d_slots, (uint64_t)alloc_slots * slot);
     HIP_OK(hipMemset(d->d_slots, 0, (uint64_t)alloc_slots * slot));   // predictor epochs start at 0
     d->n_slots = n_slots;
-    const char* sp = getenv("CLD_LONG_SPEC");
-    if (!sp || atoi(sp) != 0) {
+    if (env_long("CLD_LONG_SPEC", 1) != 0) {
       const size_t m = std::max<size_t>(1, cld_long_spec_docs(n_slots));
-      HIP_OK(hipMalloc(&d->d_spec_out, m * sizeof(cld_result)));
-      HIP_OK(hipMalloc(&d->d_spec_take, m * sizeof(uint32_t)));
+      ALLOC_OK(d->d_spec_out, m);
+      ALLOC_OK(d->d_spec_take, m);
     }
   }
-  if (const char* e = getenv("CLD_FAULT_DOC")) d->fault_doc = (uint32_t)strtoul(e, nullptr, 10);
+  d->fault_doc = (uint32_t)env_u64("CLD_FAULT_DOC", 0xFFFFFFFFu);
   if (const char* e = getenv("CLD_DEBUG_DOC")) {
     d->dbg_doc = (uint32_t)atoll(e);
-    HIP_OK(hipMalloc(&d->d_dbg, 64u << 20));
+    ALLOC_OK(d->d_dbg, 64u << 18);   // 64 MB of words
   }
-  if (const char* e = getenv("CLD_TRACE")) {
-    if (atoi(e) > 0 && n_slots > 0) {
-      HIP_OK(hipHostMalloc((void**)&d->h_trace, (size_t)n_slots * 16, hipHostMallocCoherent | hipHostMallocMapped));
-      memset(d->h_trace, 0xFF, (size_t)n_slots * 16);
-      d->trace_timeout = 20.0;
-      if (const char* t = getenv("CLD_TRACE_TIMEOUT")) d->trace_timeout = atof(t);
-    }
+  if (env_long("CLD_TRACE", 0) > 0 && n_slots > 0) {
+    ALLOC_OK(d->h_trace, (size_t)n_slots * 4);
+    memset(d->h_trace, 0xFF, (size_t)n_slots * 16);
+    d->trace_timeout = 20.0;
+    if (const char* t = getenv("CLD_TRACE_TIMEOUT")) d->trace_timeout = atof(t);
   }
   return CLD_OK;
 }
+#undef ALLOC_OK
 
 constexpr uint32_t kStripFlags = CLD_FLAG_STRIP_EXTRAS | CLD_FLAG_CSTRING;
 // flags that put a preparation step in front of the kernels (such batches take the streamed path)
@@ -701,9 +751,8 @@ constexpr uint32_t kPublicFlags = kCldFlags | CLD_FLAG_DEBUG_MASK;
 // span-parallel scoring splits their many-span pages: 1 caller 96.6K ->
 // 106K docs/s (p99 34 -> 17 ms), 32 callers 699K -> 875K
 // (profiles/round5_req_staged_ab.jsonl).
-uint32_t small_long_list(const Device* d) {
-  (void)d;
-  static const long v = getenv("CLD_LONG_SMALL") ? atol(getenv("CLD_LONG_SMALL")) : -1;
+uint32_t small_long_list() {
+  static const long v = env_long("CLD_LONG_SMALL", -1);
   return v >= 0 ? (uint32_t)v : 64u;
 }
 // ...unless it holds a document of CLD_LONG_SMALL_KB KB or more (default 0:
@@ -716,7 +765,7 @@ uint32_t small_long_list(const Device* d) {
 // pages lose the fused kernel's two-wave speculation) -- a tail-latency
 // option, not the default.
 uint64_t small_list_heavy_bytes() {
-  static const long v = getenv("CLD_LONG_SMALL_KB") ? atol(getenv("CLD_LONG_SMALL_KB")) : 0;
+  static const long v = env_long("CLD_LONG_SMALL_KB", 0);
   return v > 0 ? (uint64_t)v << 10 : ~0ull;
 }
 
@@ -726,7 +775,7 @@ uint64_t small_list_heavy_bytes() {
 // in every stage kernel, and 20 KB kept C5 on the fused kernel (18.1M
 // docs/s); with it the staged path runs C5 at 22.0M (gpurun_out/r5r).
 uint32_t heavy_kb() {
-  static const uint32_t v = getenv("CLD_LONG_HEAVY_KB") ? (uint32_t)atoi(getenv("CLD_LONG_HEAVY_KB")) : 0u;
+  static const uint32_t v = (uint32_t)env_long("CLD_LONG_HEAVY_KB", 0);
   return v;
 }
 
@@ -741,12 +790,11 @@ uint32_t heavy_kb() {
 int enqueue_prepare(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, uint64_t cap_bytes,
                     uint32_t flags, hipStream_t s, int32_t* vp = nullptr) {
   HIP_OK(hipStreamWaitEvent(s, d->done, 0));   // the previous batch may still read d_sbuf
-  if (grow(&d->d_sscr, &d->sscr_cap, cld_strip_scratch_bytes((int)n))) return CLD_ENOMEM;
+  if (d->d_sscr.reserve(cld_strip_scratch_bytes((int)n))) return CLD_ENOMEM;
   const uint8_t* src = buf;
   const uint64_t* so = offs;
   if ((flags & kStripFlags) || !(flags & CLD_FLAG_CHECK_UTF8)) {   // (neither flag: a plain copy, cld_prepare_batch)
-    if (grow(&d->d_sbuf, &d->sbuf_cap, std::max<size_t>(cap_bytes + n, 1))) return CLD_ENOMEM;
-    if (grow(&d->d_soffs, &d->soffs_cap, n + 1)) return CLD_ENOMEM;
+    if (d->d_sbuf.reserve(std::max<size_t>(cap_bytes + n, 1)) || d->d_soffs.reserve(n + 1)) return CLD_ENOMEM;
     HIP_OK(cld_launch_strip_offsets(buf, offs, (int)n, flags & kStripFlags, d->d_soffs, d->d_sscr, s));
     HIP_OK(cld_launch_strip_write(buf, offs, (int)n, flags & kStripFlags, d->d_soffs, d->d_sbuf, s));
     src = d->d_sbuf;
@@ -754,13 +802,12 @@ int enqueue_prepare(Device* d, const uint8_t* buf, const uint64_t* offs, size_t 
   }
   if (flags & CLD_FLAG_CHECK_UTF8) {
     if (!vp) {
-      if (grow(&d->d_vp, &d->vp_cap, std::max<size_t>(n, 1))) return CLD_ENOMEM;
+      if (d->d_vp.reserve(std::max<size_t>(n, 1))) return CLD_ENOMEM;
       vp = d->d_vp;
     }
-    if (grow(&d->d_cbuf, &d->cbuf_cap, std::max<size_t>(cap_bytes + n, 1))) return CLD_ENOMEM;
-    if (grow(&d->d_coffs, &d->coffs_cap, n + 1)) return CLD_ENOMEM;
+    if (d->d_cbuf.reserve(std::max<size_t>(cap_bytes + n, 1)) || d->d_coffs.reserve(n + 1)) return CLD_ENOMEM;
     HIP_OK(cld_launch_valid_prefix(src, so, (int)n, vp, cap_bytes + n, s));
-    HIP_OK(cld_launch_valid_lens(so, (int)n, vp, (uint64_t*)d->d_sscr, s));
+    HIP_OK(cld_launch_valid_lens(so, (int)n, vp, (uint64_t*)(uint8_t*)d->d_sscr, s));
     HIP_OK(cld_launch_scan_lengths((int)n, d->d_coffs, d->d_sscr, s));
     HIP_OK(cld_launch_valid_copy(src, so, (int)n, d->d_coffs, d->d_cbuf, cap_bytes + n, s));
     d->chk_offs = so;
@@ -799,27 +846,25 @@ int enqueue(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, cld_r
   const uint8_t *hbuf = nullptr, *hflag = nullptr;
   uint32_t *hpos = nullptr, *hgap = nullptr;
   if (special && html_bytes) {
-    if (grow(&d->d_hbuf, &d->hbuf_cap, html_bytes) || grow(&d->d_hflag, &d->hflag_cap, html_bytes)) return CLD_ENOMEM;
+    if (d->d_hbuf.reserve(html_bytes) || d->d_hflag.reserve(html_bytes)) return CLD_ENOMEM;
     hbuf = d->d_hbuf - html_base;
     hflag = d->d_hflag - html_base;
     // pages of kMaxScriptBytes and more also get each rewritten byte's page
     // offset: their span soft limit reads the raw bytes left
     if (html_bytes >= (uint64_t)kHtmlSoftMin) {
-      if (grow(&d->d_hpos, &d->hpos_cap, 2 * html_bytes)) return CLD_ENOMEM;
+      if (d->d_hpos.reserve(2 * html_bytes)) return CLD_ENOMEM;
       hpos = d->d_hpos - html_base;
       hgap = d->d_hpos + html_bytes - html_base;
     }
   }
-  if (grow(&d->d_requeue, &d->requeue_cap, std::max<size_t>(n, 1))) return CLD_ENOMEM;
-  if (grow(&d->d_requeue2, &d->requeue2_cap, std::max<size_t>(n, 1))) return CLD_ENOMEM;
-  if (d->n_slots > 0 && d->long_order) {
-    if (grow(&d->d_lsorted, &d->lsorted_cap, std::max<size_t>(n, 1))) return CLD_ENOMEM;
-    if (grow(&d->d_lkey, &d->lkey_cap, std::max<size_t>(n, 1))) return CLD_ENOMEM;
-  }
+  const size_t n1 = std::max<size_t>(n, 1);
+  if (d->d_requeue.reserve(n1) || d->d_requeue2.reserve(n1)) return CLD_ENOMEM;
+  if (d->n_slots > 0 && d->long_order && (d->d_lsorted.reserve(n1) || d->d_lkey.reserve(n1))) return CLD_ENOMEM;
   if (d->ev_used == d->ev_pool.size()) {
-    std::array<hipEvent_t, 4> t{};
+    hipEvent_t t[4]{};
     for (auto& e : t) HIP_OK(hipEventCreate(&e));
-    d->ev_pool.push_back(t);
+    d->ev_pool.emplace_back();
+    for (int k = 0; k < 4; ++k) d->ev_pool.back()[k].h = t[k];
   }
   auto& ev = d->ev_pool[d->ev_used++];
   HIP_OK(hipStreamWaitEvent(s, d->done, 0));   // serialise with the previous batch's scratch use
@@ -854,23 +899,22 @@ int enqueue(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, cld_r
     // than k_wave takes.  A list that short goes whole to the fused kernel
     // anyway, so the eight staged launches are skipped (each costs its
     // dispatch even when its list is empty: ~60 us per chunk of tweets)
-    const bool staged = d->staged && !d->h_trace && !d->d_dbg && !d->d_prof &&
-                        !(long_hint >= 0 && small_long_list(d) > 0 && long_hint <= (int64_t)small_long_list(d));
+    const bool staged = d->staged && !d->fused_diagnostics() &&
+                        !(long_hint >= 0 && small_long_list() > 0 && long_hint <= (int64_t)small_long_list());
     int ctr_total = kCtrRequeue, ctr_deq = kCtrDequeue;
     if (staged) {
-      if (grow(&d->d_meta, &d->meta_cap, std::max<size_t>(n, 1))) return CLD_ENOMEM;
-      if (grow(&d->d_stlists, &d->stlists_cap, 3 * std::max<size_t>(n, 1))) return CLD_ENOMEM;
-      const size_t c = d->stlists_cap / 3;
+      if (d->d_meta.reserve(n1) || d->d_stlists.reserve(3 * n1)) return CLD_ENOMEM;
+      const size_t c = d->d_stlists.capacity() / 3;
       uint32_t* fall = d->d_stlists + 2 * c;
       // span-parallel lists: documents (n each, passes 1 and 2) and groups
       // (gcap each; a document whose groups find no room takes the fused kernel)
-      const size_t np = std::max<size_t>(n, 1), gcap = std::max<size_t>(4 * np, 1u << 16);
-      if (grow(&d->d_parlists, &d->parlists_cap, 2 * np + 4 * gcap)) return CLD_ENOMEM;
+      const size_t np = n1, gcap = std::max<size_t>(4 * np, 1u << 16);
+      if (d->d_parlists.reserve(2 * np + 4 * gcap)) return CLD_ENOMEM;
       // a list of at most small_long_list() documents (64) goes whole to the
       // fused kernel: small batches keep its two-wave speculation (section 6)
       // (the host's count says the list is longer than that, or holds a
       // document of small_list_heavy_bytes() or more: no list goes whole)
-      const uint32_t small_total = long_hint > (int64_t)small_long_list(d) ? 0u : small_long_list(d);
+      const uint32_t small_total = long_hint > (int64_t)small_long_list() ? 0u : small_long_list();
       HIP_OK(cld_launch_staged(d->d_T, buf, offs, list, out, d->d_slots, d->st_waves, d->d_store, d->store_bytes,
                                d->d_meta, d->d_stlists, d->d_stlists + c, fall, ctr, cflags, special,
                                priors, hbuf, hflag, hpos, hgap, d->fault_doc, small_total,
@@ -896,8 +940,7 @@ int enqueue(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, cld_r
 // short_docs: finished by k_wave; long_docs: by k_long (or the staged path)
 // on the parallel span builder; general_docs: by k_long on the sequential
 // span source (cld_seq.hip).
-void add_counters(Device* d, const uint32_t* c, uint64_t docs, cld_batch_stats* st) {
-  (void)d;
+void add_counters(const uint32_t* c, uint64_t docs, cld_batch_stats* st) {
   const uint64_t shorts = docs - c[kCtrRequeue];
   st->docs += docs;
   st->general_docs += c[kCtrSeq];
@@ -926,7 +969,7 @@ int collect_stats(Device* d) {
   HIP_OK(hipEventElapsedTime(&ms3, d->ev[2], d->ev[3]));
   cld_batch_stats& st = d->last;
   memset(&st, 0, sizeof(st));
-  add_counters(d, c, d->last_n, &st);
+  add_counters(c, d->last_n, &st);
   st.short_ms = ms1;
   st.long_ms = ms2;
   st.general_ms = ms3;
@@ -976,11 +1019,7 @@ void watch_trace(Device* d, hipStream_t s) {
 // 16 MB chunks 7.0 ms, 32 MB 6.3 ms, 64 MB 6.2 ms per 1M documents;
 // gpurun_out/r4g).  CLD_CHUNK_MB overrides the byte limit.
 uint64_t chunk_bytes() {
-  static const uint64_t v = [] {
-    uint64_t mb = 64;
-    if (const char* e = getenv("CLD_CHUNK_MB")) mb = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
-    return mb << 20;
-  }();
+  static const uint64_t v = std::max<uint64_t>(1, env_u64("CLD_CHUNK_MB", 64)) << 20;
   return v;
 }
 
@@ -991,17 +1030,6 @@ bool host_pinned(const void* p) {
     return false;
   }
   return a.type == hipMemoryTypeHost;
-}
-
-template <class T>
-int grow_host(T** p, size_t* cap, size_t need) {
-  if (*cap >= need) return CLD_OK;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  size_t n = std::max(need, *cap * 3 / 2);
-  if (hipHostMalloc((void**)p, n * sizeof(T), hipHostMallocDefault) != hipSuccess) { *cap = 0; return CLD_ENOMEM; }
-  *cap = n;
-  return CLD_OK;
 }
 
 // Staging copies (pageable caller memory <-> pinned slots) on a persistent
@@ -1049,9 +1077,8 @@ class CopyPool {
     }
   };
   CopyPool() {
-    int t = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-    if (const char* e = getenv("CLD_COPY_THREADS")) t = std::max(1, atoi(e));
-    workers_ = t - 1;
+    const int dflt = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    workers_ = std::max(1, (int)env_long("CLD_COPY_THREADS", dflt)) - 1;
     for (int i = 0; i < workers_; ++i) std::thread([this] { work(); }).detach();
   }
   void work() {
@@ -1092,12 +1119,8 @@ void par_copy(void* dst, const void* src, size_t n) { CopyPool::get().copy(dst, 
 // (hipHostRegister) instead of staged chunk by chunk through pinned copies,
 // above CLD_HOST_REGISTER_MB of document text (default 64; 0 = never).
 uint64_t register_min_bytes() {
-  static const uint64_t v = [] {
-    uint64_t mb = 64;
-    if (const char* e = getenv("CLD_HOST_REGISTER_MB")) mb = strtoull(e, nullptr, 10);
-    return mb ? mb << 20 : ~0ull;
-  }();
-  return v;
+  static const uint64_t mb = env_u64("CLD_HOST_REGISTER_MB", 64);
+  return mb ? mb << 20 : ~0ull;
 }
 
 // Page-locks [p, p + bytes) for the life of the object when it is not pinned already.
@@ -1128,22 +1151,87 @@ struct HostReg {
 // marked them); internal, never returned to a caller.
 constexpr int kDocsFailed = 1;
 
-int run_host_stream(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, cld_result* out, uint32_t flags,
-                    const uint8_t* special = nullptr, const uint32_t* priors = nullptr, bool html = false,
-                    int32_t* vp_out = nullptr) {
+struct DocRef {
+  const uint8_t* p;
+  size_t len;
+};
+
+// A host batch, or a run of its documents: what every path from the entry
+// points down to run_host_stream / run_vec_shard works on.
+struct Batch {
+  const uint8_t* buf;
+  const uint64_t* offs;                // n + 1 offsets into buf, as the caller wrote them
+  size_t n;
+  cld_result* out;
+  uint32_t flags = 0;
+  const uint8_t* special = nullptr;    // cld_detect_batch_ex (nullable): routing bits, one per document,
+  const uint32_t* priors = nullptr;    //   and ApplyHints langprobs, 16 per document
+  bool html = false;
+  int32_t* vp_out = nullptr;           // cld_detect_batch_checked (nullable): the valid prefixes go here
+
+  DocRef doc(size_t i) const { return DocRef{buf + offs[i], (size_t)(offs[i + 1] - offs[i])}; }
+  // documents [first, first + count)
+  Batch slice(size_t first, size_t count) const {
+    Batch s = *this;
+    s.offs += first;
+    s.n = count;
+    s.out += first;
+    if (special) s.special += first;
+    if (priors) s.priors += 16 * first;
+    if (vp_out) s.vp_out += first;
+    return s;
+  }
+};
+
+// Documents idx[] of a batch gathered into a fresh one to be redone: packed
+// text (doc(i) fetches document i), offsets from 0, the routing bits and
+// priors where the batch has them, and room for the results.  b is the view
+// over them; it delivers no valid prefixes (a redo only scores).
+struct Gathered {
+  std::vector<uint8_t> text, special;
+  std::vector<uint64_t> offs{0};
+  std::vector<uint32_t> priors;
+  std::vector<cld_result> out;
+  Batch b;
+  template <class Idx, class DocFn>
+  Gathered(const Batch& src, const std::vector<Idx>& idx, DocFn doc) : out(idx.size()), b(src) {
+    for (Idx i : idx) {
+      const DocRef r = doc(i);
+      text.insert(text.end(), r.p, r.p + r.len);
+      offs.push_back(text.size());
+      if (src.special) special.push_back(src.special[i]);
+      if (src.priors) priors.insert(priors.end(), src.priors + 16 * i, src.priors + 16 * i + 16);
+    }
+    b.buf = text.empty() ? (const uint8_t*)"" : text.data();   // (every document empty: still a pointer)
+    b.offs = offs.data();
+    b.n = idx.size();
+    b.out = out.data();
+    b.vp_out = nullptr;
+    if (src.special) b.special = special.data();
+    if (src.priors) b.priors = priors.data();
+  }
+  template <class Idx>
+  Gathered(const Batch& src, const std::vector<Idx>& idx) : Gathered(src, idx, [&](size_t i) { return src.doc(i); }) {}
+  Gathered(const Gathered&) = delete;
+  Gathered& operator=(const Gathered&) = delete;
+};
+
+// *st_out (nullable): this call's statistics, the ones it also leaves in d->last.
+int run_host_stream(Device* d, const Batch& b, cld_batch_stats* st_out) {
   std::lock_guard<std::mutex> lk(d->mu);
   HIP_OK(hipSetDevice(d->id));
   d->ev_used = 0;
-  bool in_pinned = host_pinned(buf + offs[0]) && host_pinned(offs);
-  bool out_pinned = host_pinned(out);
+  bool in_pinned = host_pinned(b.buf + b.offs[0]) && host_pinned(b.offs);
+  bool out_pinned = host_pinned(b.out);
   // (declared before any DMA is enqueued: unregistered only after the drain below)
   HostReg reg_buf, reg_offs, reg_out;
-  if (offs[n] - offs[0] >= register_min_bytes()) {
+  if (b.offs[b.n] - b.offs[0] >= register_min_bytes()) {
     if (!in_pinned) {
-      in_pinned = reg_buf.take(buf + offs[0], offs[n] - offs[0]) && reg_offs.take(offs, (n + 1) * sizeof(uint64_t));
+      in_pinned = reg_buf.take(b.buf + b.offs[0], b.offs[b.n] - b.offs[0]) &&
+                  reg_offs.take(b.offs, (b.n + 1) * sizeof(uint64_t));
       if (!in_pinned) reg_buf.release();
     }
-    if (!out_pinned) out_pinned = reg_out.take(out, n * sizeof(cld_result));
+    if (!out_pinned) out_pinned = reg_out.take(b.out, b.n * sizeof(cld_result));
   }
   // chunk plan.  The first chunks ramp up (1/8, 1/4, 1/2 of the chunk size):
   // nothing runs until chunk 0 is uploaded, and an upload (~53 GB/s) outruns
@@ -1155,24 +1243,23 @@ int run_host_stream(Device* d, const uint8_t* buf, const uint64_t* offs, size_t 
   // times as large and without the ramp (a coalesced batch of requests is
   // then one launch; C5 requests: 8 callers 193K -> 299K, 64 callers
   // 404K -> 863K docs/s).
-  const bool tail_bound = offs[n] - offs[0] > (uint64_t)n * kWaveCap;
+  const bool tail_bound = b.offs[b.n] - b.offs[0] > (uint64_t)b.n * kWaveCap;
   std::vector<size_t> cut{0};
-  while (cut.back() < n) {
+  while (cut.back() < b.n) {
     const size_t a = cut.back();
     const size_t ci = cut.size() - 1;
     const uint64_t kChunkBytes = tail_bound ? 4 * chunk_bytes()
                                             : std::max<uint64_t>(1u << 20, chunk_bytes() >> (ci < 3 ? 3 - ci : 0));
     const size_t kChunkDocs = (size_t)(kChunkBytes >> 7);    // 8K documents per MB
-    size_t lo = a + 1, hi = std::min(n, a + kChunkDocs);     // largest b <= hi with bytes <= kChunkBytes (>= 1 doc)
+    size_t lo = a + 1, hi = std::min(b.n, a + kChunkDocs);   // largest cut <= hi with bytes <= kChunkBytes (>= 1 doc)
     while (lo < hi) {
       const size_t mid = (lo + hi + 1) / 2;
-      if (offs[mid] - offs[a] <= kChunkBytes) lo = mid; else hi = mid - 1;
+      if (b.offs[mid] - b.offs[a] <= kChunkBytes) lo = mid; else hi = mid - 1;
     }
     cut.push_back(lo);
   }
   const size_t nch = cut.size() - 1;
-  if (grow_host(&d->h_ctr, &d->h_ctr_cap, nch * kCtrSlots)) return CLD_ENOMEM;
-  if (grow(&d->d_ctrs, &d->ctrs_cap, nch * kCtrSlots)) return CLD_ENOMEM;
+  if (d->h_ctr.reserve(nch * kCtrSlots) || d->d_ctrs.reserve(nch * kCtrSlots)) return CLD_ENOMEM;
   // every chunk's counters zeroed at once here, read back at once after the loop
   HIP_OK(hipMemsetAsync(d->d_ctrs, 0, nch * kCtrSlots * sizeof(uint32_t), d->stream));
   // both slots sized for the largest chunk up front (the previous call has
@@ -1181,21 +1268,21 @@ int run_host_stream(Device* d, const uint8_t* buf, const uint64_t* offs, size_t 
   uint64_t max_bytes = 1;
   for (size_t c = 0; c < nch; ++c) {
     max_m = std::max(max_m, cut[c + 1] - cut[c]);
-    max_bytes = std::max<uint64_t>(max_bytes, offs[cut[c + 1]] - offs[cut[c]]);
+    max_bytes = std::max<uint64_t>(max_bytes, b.offs[cut[c + 1]] - b.offs[cut[c]]);
   }
   for (Device::Slot& h : d->hs) {
-    int r = grow(&h.d_in, &h.d_in_cap, max_bytes);
-    if (!r) r = grow(&h.d_offs, &h.d_offs_cap, max_m + 1);
-    if (!r) r = grow(&h.d_out, &h.d_out_cap, max_m);
-    if (!r && !in_pinned) r = grow_host(&h.h_in, &h.h_in_cap, max_bytes);
-    if (!r && !in_pinned) r = grow_host(&h.h_offs, &h.h_offs_cap, max_m + 1);
-    if (!r && !out_pinned) r = grow_host(&h.h_out, &h.h_out_cap, max_m);
-    if (!r && special) r = grow(&h.d_sp, &h.d_sp_cap, max_m);
-    if (!r && special) r = grow_host(&h.h_sp, &h.h_sp_cap, max_m);
-    if (!r && priors) r = grow(&h.d_pri, &h.d_pri_cap, 16 * max_m);
-    if (!r && priors) r = grow_host(&h.h_pri, &h.h_pri_cap, 16 * max_m);
-    if (!r && (flags & CLD_FLAG_CHECK_UTF8)) r = grow(&h.d_vp, &h.d_vp_cap, std::max<size_t>(max_m, 1));
-    if (!r && vp_out) r = grow_host(&h.h_vp, &h.h_vp_cap, std::max<size_t>(max_m, 1));
+    int r = h.d_in.reserve(max_bytes);
+    if (!r) r = h.d_offs.reserve(max_m + 1);
+    if (!r) r = h.d_out.reserve(max_m);
+    if (!r && !in_pinned) r = h.h_in.reserve(max_bytes);
+    if (!r && !in_pinned) r = h.h_offs.reserve(max_m + 1);
+    if (!r && !out_pinned) r = h.h_out.reserve(max_m);
+    if (!r && b.special) r = h.d_sp.reserve(max_m);
+    if (!r && b.special) r = h.h_sp.reserve(max_m);
+    if (!r && b.priors) r = h.d_pri.reserve(16 * max_m);
+    if (!r && b.priors) r = h.h_pri.reserve(16 * max_m);
+    if (!r && (b.flags & CLD_FLAG_CHECK_UTF8)) r = h.d_vp.reserve(std::max<size_t>(max_m, 1));
+    if (!r && b.vp_out) r = h.h_vp.reserve(std::max<size_t>(max_m, 1));
     if (r) return r;
   }
   int rc = CLD_OK;
@@ -1214,27 +1301,27 @@ int run_host_stream(Device* d, const uint8_t* buf, const uint64_t* offs, size_t 
     Device::Slot& h = d->hs[c & 1];
     if (h.busy) HIP_BRK(hipEventSynchronize(h.up))
     const size_t a = cut[c], m = cut[c + 1] - a;
-    const uint64_t base = offs[a], bytes = offs[a + m] - base;
-    const uint8_t* src_in = buf + base;
-    const uint64_t* src_offs = offs + a;
+    const uint64_t base = b.offs[a], bytes = b.offs[a + m] - base;
+    const uint8_t* src_in = b.buf + base;
+    const uint64_t* src_offs = b.offs + a;
     if (!in_pinned) {
       par_copy(h.h_in, src_in, bytes);
       memcpy(h.h_offs, src_offs, (m + 1) * sizeof(uint64_t));
       src_in = h.h_in;
       src_offs = h.h_offs;
     }
-    cld_result* dst = out + a;
-    if (special) {           // per-document routing bits (and priors) for this chunk, staged pinned
-      memcpy(h.h_sp, special + a, m);
-      if (priors) memcpy(h.h_pri, priors + 16 * a, 16 * m * sizeof(uint32_t));
+    cld_result* dst = b.out + a;
+    if (b.special) {           // per-document routing bits (and priors) for this chunk, staged pinned
+      memcpy(h.h_sp, b.special + a, m);
+      if (b.priors) memcpy(h.h_pri, b.priors + 16 * a, 16 * m * sizeof(uint32_t));
     }
     // upload (after the slot's previous kernels stopped reading its device buffers)
     HIP_BRK(hipStreamWaitEvent(d->up_stream, h.comp, 0))
     if (bytes) HIP_BRK(hipMemcpyAsync(h.d_in, src_in, bytes, hipMemcpyHostToDevice, d->up_stream))
     HIP_BRK(hipMemcpyAsync(h.d_offs, src_offs, (m + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, d->up_stream))
-    if (special) {
+    if (b.special) {
       HIP_BRK(hipMemcpyAsync(h.d_sp, h.h_sp, m, hipMemcpyHostToDevice, d->up_stream))
-      if (priors)
+      if (b.priors)
         HIP_BRK(hipMemcpyAsync(h.d_pri, h.h_pri, 16 * m * sizeof(uint32_t), hipMemcpyHostToDevice, d->up_stream))
     }
     HIP_BRK(hipEventRecord(h.up, d->up_stream))
@@ -1250,8 +1337,8 @@ int run_host_stream(Device* d, const uint8_t* buf, const uint64_t* offs, size_t 
     // fused kernel's cap needs the staged path whatever the count
     int64_t long_hint = 0;
     {
-      const int64_t lim = (int64_t)small_long_list(d);
-      const uint64_t* o = offs + a;
+      const int64_t lim = (int64_t)small_long_list();
+      const uint64_t* o = b.offs + a;
       const uint64_t heavy = small_list_heavy_bytes();
       for (size_t i = 0; i < m && long_hint <= lim; ++i) {
         const uint64_t len = o[i + 1] - o[i];
@@ -1259,19 +1346,13 @@ int run_host_stream(Device* d, const uint8_t* buf, const uint64_t* offs, size_t 
         if (len > kLongDocCap - 64 || len >= heavy) long_hint = lim + 1;
       }
     }
-    if (flags & kPrepFlags) {
-      // (the prepared batch's offsets start at 0: HTML pages are rewritten with base 0)
-      const bool chk = (flags & CLD_FLAG_CHECK_UTF8) != 0;
-      if ((rc = enqueue_prepare(d, kbuf, h.d_offs, m, bytes, flags, d->stream, chk ? h.d_vp : nullptr))) break;
-      rc = enqueue(d, d->p_buf, d->p_offs, m, h.d_out, d->stream, special ? h.d_sp : nullptr,
-                   (special && priors) ? h.d_pri : nullptr, flags, 0, (special && html) ? bytes : 0,
-                   d->d_ctrs + c * kCtrSlots, long_hint);
-      if (rc == CLD_OK && chk) rc = enqueue_fixup(d, h.d_out, m, d->stream);
-    } else {
-      rc = enqueue(d, kbuf, h.d_offs, m, h.d_out, d->stream, special ? h.d_sp : nullptr,
-                   (special && priors) ? h.d_pri : nullptr, flags, base, (special && html) ? bytes : 0,
-                   d->d_ctrs + c * kCtrSlots, long_hint);
-    }
+    const bool prep = (b.flags & kPrepFlags) != 0, chk = (b.flags & CLD_FLAG_CHECK_UTF8) != 0;
+    if (prep && (rc = enqueue_prepare(d, kbuf, h.d_offs, m, bytes, b.flags, d->stream, chk ? h.d_vp : nullptr))) break;
+    // (the prepared batch's offsets start at 0: HTML pages are rewritten with base 0)
+    rc = enqueue(d, prep ? d->p_buf : kbuf, prep ? d->p_offs : h.d_offs, m, h.d_out, d->stream,
+                 b.special ? h.d_sp : nullptr, (b.special && b.priors) ? h.d_pri : nullptr, b.flags, prep ? 0 : base,
+                 (b.special && b.html) ? bytes : 0, d->d_ctrs + c * kCtrSlots, long_hint);
+    if (rc == CLD_OK && chk) rc = enqueue_fixup(d, h.d_out, m, d->stream);
     if (rc) break;
     HIP_BRK(hipEventRecord(h.comp, d->stream))
     // download (chunk c-2's results out of h_out first)
@@ -1279,11 +1360,11 @@ int run_host_stream(Device* d, const uint8_t* buf, const uint64_t* offs, size_t 
     HIP_BRK(hipStreamWaitEvent(d->down_stream, h.comp, 0))
     HIP_BRK(hipMemcpyAsync(out_pinned ? dst : h.h_out, h.d_out, m * sizeof(cld_result), hipMemcpyDeviceToHost,
                           d->down_stream))
-    if (vp_out)
+    if (b.vp_out)
       HIP_BRK(hipMemcpyAsync(h.h_vp, h.d_vp, m * sizeof(int32_t), hipMemcpyDeviceToHost, d->down_stream))
     HIP_BRK(hipEventRecord(h.down, d->down_stream))
     h.pending_n = m;
-    h.pending_vp = vp_out ? vp_out + a : nullptr;
+    h.pending_vp = b.vp_out ? b.vp_out + a : nullptr;
     h.pending_dst = out_pinned ? nullptr : dst;
     h.busy = true;
   }
@@ -1298,7 +1379,7 @@ int run_host_stream(Device* d, const uint8_t* buf, const uint64_t* offs, size_t 
   // an upload or a kernel enqueued before an error in the loop may still read
   // the caller's (possibly registered) buffers: all three streams drain
   // before the HostReg objects above unregister them
-  for (hipStream_t q : {d->up_stream, d->stream, d->down_stream})
+  for (hipStream_t q : {d->up_stream.h, d->stream.h, d->down_stream.h})
     if (hipStreamSynchronize(q) != hipSuccess && rc == CLD_OK) rc = CLD_EFAULT;
   if (rc) return rc;
   if (d->d_dbg) {             // debug: write the dumped words to $CLD_DEBUG_OUT
@@ -1315,7 +1396,7 @@ int run_host_stream(Device* d, const uint8_t* buf, const uint64_t* offs, size_t 
   memset(&st, 0, sizeof(st));
   bool err = false;
   for (size_t c = 0; c < nch; ++c) {
-    add_counters(d, d->h_ctr + c * kCtrSlots, cut[c + 1] - cut[c], &st);
+    add_counters(d->h_ctr + c * kCtrSlots, cut[c + 1] - cut[c], &st);
     err |= d->h_ctr[c * kCtrSlots + kCtrError] != 0;
   }
   for (size_t i = 0; i < d->ev_used; ++i) {
@@ -1326,6 +1407,7 @@ int run_host_stream(Device* d, const uint8_t* buf, const uint64_t* offs, size_t 
     st.short_ms += x; st.long_ms += y; st.general_ms += z;
   }
   d->stats_pending = false;
+  if (st_out) *st_out = st;
   return err ? kDocsFailed : CLD_OK;
 }
 
@@ -1340,31 +1422,22 @@ int run_host_stream(Device* d, const uint8_t* buf, const uint64_t* offs, size_t 
 // streamed path; results are the same whichever path finishes a document.
 // CLD_TINY=0 turns it off (A/B).
 bool tiny_enabled() {
-  static const bool v = !(getenv("CLD_TINY") && atoi(getenv("CLD_TINY")) == 0);
+  static const bool v = env_long("CLD_TINY", 1) != 0;
   return v;
 }
 
-bool tiny_batch(const Device* d, const uint64_t* offs, size_t n, uint32_t flags, const uint8_t* special,
-                const uint32_t* priors) {
-  if (n == 0 || n > kTinyDocs || special || priors || (flags & kPrepFlags) || !tiny_enabled()) return false;
-  if (d->d_dbg || d->h_trace || d->d_prof || d->fault_doc != 0xFFFFFFFFu) return false;   // diagnostics
-  uint64_t bad = 0;
-  for (size_t i = 0; i < n; ++i) bad |= (uint64_t)(offs[i + 1] - offs[i] > (uint64_t)kWaveCap);
-  return bad == 0;
+bool tiny_batch(const Device* d, const Batch& b) {
+  if (b.n == 0 || b.n > kTinyDocs || b.special || b.priors || (b.flags & kPrepFlags) || !tiny_enabled()) return false;
+  return !d->diagnostics() && all_fit_wave(b.offs, b.n);
 }
 
 // CLD_TINY_ZC=1: k_wave reads the documents from the pinned block and
 // writes the results into it over PCIe (no DMA at all: one launch and one
 // synchronisation per call); default: one upload and one download.
 bool tiny_zero_copy() {
-  static const bool v = getenv("CLD_TINY_ZC") && atoi(getenv("CLD_TINY_ZC")) != 0;
+  static const bool v = env_long("CLD_TINY_ZC", 0) != 0;
   return v;
 }
-
-struct DocRef {
-  const uint8_t* p;
-  size_t len;
-};
 
 // k_wave alone over n documents of at most kWaveCap bytes in tiny slot t (the
 // caller holds t->mu): doc(i) -> DocRef, written straight into the slot's
@@ -1385,16 +1458,14 @@ int tiny_run_slot(Device* d, TinySlot* t, size_t n, DocFn doc, cld_result* out, 
     bytes += r.len;
   }
   ho[n] = bytes;
-  if (tiny_zero_copy()) {
-    HIP_OK(cld_launch_wave_only(&d->T, t->hd + text_off, (const uint64_t*)(t->hd + kTinyOffsOff), (int)n,
-                                (cld_result*)(t->hd + out_off), nullptr, nullptr, flags & kCldFlags, t->s));
-  } else {
-    HIP_OK(hipMemcpyAsync(t->dv + kTinyOffsOff, t->h + kTinyOffsOff, text_off - kTinyOffsOff + bytes,
+  const bool zc = tiny_zero_copy();
+  uint8_t* const dev = zc ? t->hd : (uint8_t*)t->dv;         // the block as k_wave addresses it
+  if (!zc)
+    HIP_OK(hipMemcpyAsync(dev + kTinyOffsOff, t->h + kTinyOffsOff, text_off - kTinyOffsOff + bytes,
                           hipMemcpyHostToDevice, t->s));
-    HIP_OK(cld_launch_wave_only(&d->T, t->dv + text_off, (const uint64_t*)(t->dv + kTinyOffsOff), (int)n,
-                                (cld_result*)(t->dv + out_off), nullptr, nullptr, flags & kCldFlags, t->s));
-    HIP_OK(hipMemcpyAsync(t->h + out_off, t->dv + out_off, n * sizeof(cld_result), hipMemcpyDeviceToHost, t->s));
-  }
+  HIP_OK(cld_launch_wave_only(&d->T, dev + text_off, (const uint64_t*)(dev + kTinyOffsOff), (int)n,
+                              (cld_result*)(dev + out_off), nullptr, nullptr, flags & kCldFlags, t->s));
+  if (!zc) HIP_OK(hipMemcpyAsync(t->h + out_off, dev + out_off, n * sizeof(cld_result), hipMemcpyDeviceToHost, t->s));
   HIP_OK(hipStreamSynchronize(t->s));
   memcpy(out, t->h + out_off, n * sizeof(cld_result));
   return CLD_OK;
@@ -1413,19 +1484,11 @@ int tiny_redo_requeued(Device* d, size_t n, DocFn doc, cld_result* out, uint32_t
   st->short_docs = n - rq;
   st->passes[0] = n - rq;
   if (rq == 0) return CLD_OK;
-  std::vector<uint8_t> gb;
-  std::vector<uint64_t> go{0};
-  for (uint32_t i : list) {
-    const DocRef r = doc(i);
-    gb.insert(gb.end(), r.p, r.p + r.len);
-    go.push_back(gb.size());
-  }
-  std::vector<cld_result> gout(rq);
-  const int rc = run_host_stream(d, gb.data(), go.data(), rq, gout.data(), flags);
+  Gathered g(Batch{nullptr, nullptr, n, out, flags}, list, doc);
+  cld_batch_stats s2{};                                // the streamed call's counts for the re-queued documents
+  const int rc = run_host_stream(d, g.b, &s2);
   if (rc != CLD_OK && rc != kDocsFailed) return rc;
-  for (uint32_t k = 0; k < rq; ++k) out[list[k]] = gout[k];
-  std::lock_guard<std::mutex> dl(d->mu);
-  const cld_batch_stats s2 = d->last;                  // the streamed call's counts for the re-queued documents
+  for (uint32_t k = 0; k < rq; ++k) out[list[k]] = g.out[k];
   st->long_docs = s2.long_docs;
   st->general_docs = s2.general_docs;
   st->short_docs += s2.short_docs;
@@ -1435,23 +1498,34 @@ int tiny_redo_requeued(Device* d, size_t n, DocFn doc, cld_result* out, uint32_t
   return rc;
 }
 
-int run_tiny(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, cld_result* out, uint32_t flags) {
-  TinySlot* t = nullptr;
-  std::unique_lock<std::mutex> lk;
-  const int ns = tiny_slots();
-  for (int k = 0; k < ns; ++k) {
-    std::unique_lock<std::mutex> l(d->tiny[k].mu, std::try_to_lock);
-    if (l.owns_lock()) { t = &d->tiny[k]; lk = std::move(l); break; }
+// One call on tiny slot t, whose mu the caller has locked (it is released
+// here, as soon as k_wave's results are out of the slot): k_wave, then the
+// redo of what it handed on.  kDocsFailed: see tiny_doc_rc.
+template <class DocFn>
+int tiny_call(Device* d, TinySlot* t, size_t n, DocFn doc, cld_result* out, uint32_t flags, cld_batch_stats* st) {
+  {
+    std::lock_guard<std::mutex> lk(t->mu, std::adopt_lock);
+    if (int rc = tiny_run_slot(d, t, n, doc, out, flags)) return rc;
   }
+  return tiny_redo_requeued(d, n, doc, out, flags, st);
+}
+// What a tiny call's return code means for one of its documents: kDocsFailed
+// only for a document left without a result (its caller redoes it alone).
+int tiny_doc_rc(int rc, const cld_result& r) {
+  return rc == kDocsFailed ? (r.summary_lang == CLD_LANG_FAILED ? kDocsFailed : CLD_OK) : rc;
+}
+
+int run_tiny(Device* d, const Batch& b) {
+  TinySlot* t = nullptr;
+  const int ns = tiny_slots();
+  for (int k = 0; k < ns && !t; ++k)
+    if (d->tiny[k].mu.try_lock()) t = &d->tiny[k];
   if (!t) {
     t = &d->tiny[d->tiny_rr.fetch_add(1) % ns];
-    lk = std::unique_lock<std::mutex>(t->mu);
+    t->mu.lock();
   }
-  auto doc = [&](size_t i) { return DocRef{buf + offs[i], (size_t)(offs[i + 1] - offs[i])}; };
-  if (int rc = tiny_run_slot(d, t, n, doc, out, flags)) return rc;
-  lk.unlock();
   cld_batch_stats st{};
-  const int rc = tiny_redo_requeued(d, n, doc, out, flags, &st);
+  const int rc = tiny_call(d, t, b.n, [&](size_t i) { return b.doc(i); }, b.out, b.flags, &st);
   if (rc != CLD_OK && rc != kDocsFailed) return rc;
   if (st.docs == st.short_docs) {
     std::unique_lock<std::mutex> dl(d->mu, std::try_to_lock);   // best effort: diagnostics only
@@ -1464,11 +1538,8 @@ int run_tiny(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, cld_
 }
 
 // One device's share of a host batch: run_tiny when it qualifies, else the streamed path.
-int run_host_shard(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, cld_result* out, uint32_t flags,
-                   const uint8_t* special = nullptr, const uint32_t* priors = nullptr, bool html = false,
-                   int32_t* vp_out = nullptr) {
-  if (tiny_batch(d, offs, n, flags, special, priors)) return run_tiny(d, buf, offs, n, out, flags);
-  return run_host_stream(d, buf, offs, n, out, flags, special, priors, html, vp_out);
+int run_host_shard(Device* d, const Batch& b) {
+  return tiny_batch(d, b) ? run_tiny(d, b) : run_host_stream(d, b, nullptr);
 }
 
 // Documents the kernels could not score come back marked CLD_LANG_FAILED
@@ -1481,38 +1552,24 @@ int run_host_shard(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n
 // failures, and at most kIsolateAlone of them, is each such document run
 // alone, so one document cannot take another's result with it.
 constexpr size_t kIsolateAlone = 16;
-int run_host_shard_isolating(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, cld_result* out,
-                             uint32_t flags, const uint8_t* special = nullptr, const uint32_t* priors = nullptr,
-                             bool html = false, int32_t* vp_out = nullptr) {
-  // (vp_out: the valid prefixes of a checked batch; the first run delivers them, the retries below only score)
-  int rc = run_host_shard(d, buf, offs, n, out, flags, special, priors, html, vp_out);
+int run_host_shard_isolating(Device* d, const Batch& b) {
+  // (b.vp_out: the valid prefixes of a checked batch; the first run delivers them, the retries below only score)
+  int rc = run_host_shard(d, b);
   if (rc != kDocsFailed) return rc;
   std::vector<size_t> idx;
-  for (size_t i = 0; i < n; ++i)
-    if (out[i].summary_lang == CLD_LANG_FAILED) idx.push_back(i);
-  // gather the failed documents (with their routing bits and priors) into one batch
-  std::vector<uint8_t> gb;
-  std::vector<uint64_t> go{0};
-  std::vector<uint8_t> gsp;
-  std::vector<uint32_t> gpr;
-  for (size_t i : idx) {
-    gb.insert(gb.end(), buf + offs[i], buf + offs[i + 1]);
-    go.push_back(gb.size());
-    if (special) gsp.push_back(special[i]);
-    if (priors) gpr.insert(gpr.end(), priors + 16 * i, priors + 16 * i + 16);
-  }
-  std::vector<cld_result> gout(idx.size());
-  int r = run_host_shard(d, gb.data(), go.data(), idx.size(), gout.data(), flags, special ? gsp.data() : nullptr,
-                         priors ? gpr.data() : nullptr, html);
+  for (size_t i = 0; i < b.n; ++i)
+    if (b.out[i].summary_lang == CLD_LANG_FAILED) idx.push_back(i);
+  Gathered g(b, idx);          // the failed documents (with their routing bits and priors) as one batch
+  int r = run_host_shard(d, g.b);
   if (r != CLD_OK && r != kDocsFailed) return r;          // a device error, not a document
   size_t left = 0;
   for (size_t k = 0; k < idx.size(); ++k) {
-    out[idx[k]] = gout[k];
-    if (gout[k].summary_lang != CLD_LANG_FAILED) continue;
+    b.out[idx[k]] = g.out[k];
+    if (g.out[k].summary_lang != CLD_LANG_FAILED) continue;
     if (++left > kIsolateAlone) continue;                 // stays marked: CLD_EIO below
-    const size_t i = idx[k];
-    r = run_host_shard(d, buf, offs + i, 1, out + i, flags, special ? special + i : nullptr,
-                       priors ? priors + 16 * i : nullptr, html);
+    Batch one = b.slice(idx[k], 1);
+    one.vp_out = nullptr;
+    r = run_host_shard(d, one);
     if (r != CLD_OK && r != kDocsFailed) return r;
     if (r == CLD_OK) --left;
   }
@@ -1537,54 +1594,51 @@ struct FanoutReg {
 // ResultChunkVector mode on one device: documents in sub-batches (the
 // kernel is the exact sequential pipeline; no overlap needed), each
 // document building its vector in a pool region of len + len/4 + 8 chunks,
-// then a gather into document order.  Appends the chunks of documents
-// [0, n) to *chunks and their counts to *counts.
-int run_vec_shard(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, cld_result* out,
-                  const uint8_t* special, const uint32_t* priors, std::vector<cld_chunk>* chunks,
-                  std::vector<int32_t>* counts, uint32_t cflags) {
+// then a gather into document order.  Appends the chunks of b's documents
+// to *chunks and their counts to *counts.
+int run_vec_shard(Device* d, const Batch& b, std::vector<cld_chunk>* chunks, std::vector<int32_t>* counts) {
   std::lock_guard<std::mutex> lk(d->mu);
   HIP_OK(hipSetDevice(d->id));
   Device::Vec& V = d->vec;
   // k_long<VEC> builds every vector (the parallel span builder, or for the
   // documents it cannot formulate the sequential span source), one VecSlot per
   // resident wave, allocated on the first vector call
-  if (!V.vslots && hipMalloc(&V.vslots, (uint64_t)d->n_slots * cld_vec_slot_bytes()) != hipSuccess) {
-    V.vslots = nullptr;
-    return CLD_ENOMEM;
-  }
+  if (V.vslots.reserve((uint64_t)d->n_slots * cld_vec_slot_bytes())) return CLD_ENOMEM;
   // Sub-batches as large as memory allows: a launch lasts at least as long as
   // its longest document (one wave runs it start to end), so every sub-batch
   // pays that tail once -- 32 MB sub-batches held C5 to 76K docs/s, one launch
   // for the 95 MB batch runs it at 208K.  256 MB of text takes ~5 GB of pool.
   const size_t kSub = 1024 * 1024;
-  static const uint64_t kSubBytes0 = (getenv("CLD_VEC_SUB_MB") ? (uint64_t)atoi(getenv("CLD_VEC_SUB_MB")) : 256ull) << 20;
+  static const uint64_t kSubBytes0 = (uint64_t)env_long("CLD_VEC_SUB_MB", 256) << 20;
   uint64_t kSubBytes = kSubBytes0;   // halved while the device cannot hold a sub-batch's pool
   // test hook: CLD_VEC_POOL_SMALL=1 makes first-pass pool regions too small so
   // the retry below runs (tests/test_gpu_vector.py)
-  static const bool small_pool = getenv("CLD_VEC_POOL_SMALL") && atoi(getenv("CLD_VEC_POOL_SMALL")) > 0;
-  // One sub-batch: documents [o[0], o[m]) of b (o: offsets into b), document
-  // i building its vector in a pool region of len + len/4 + 8 chunks (big: 8 len
-  // + 256); results to res, vector sizes to nch (-1: the document overflowed
-  // its pool region or an offset map), the vectors to ch in document order.
+  static const bool small_pool = env_long("CLD_VEC_POOL_SMALL", 0) > 0;
+  // One sub-batch: the documents of sb, document i building its vector in a
+  // pool region of len + len/4 + 8 chunks (big: 8 len + 256); results to
+  // sb.out, vector sizes to nch (-1: the document overflowed its pool region
+  // or an offset map), the vectors to ch in document order.
   std::vector<uint64_t> pool_off, pos;
   cld_batch_stats vst{};
-  auto sub = [&](const uint8_t* b, const uint64_t* o, size_t m, cld_result* res, const uint8_t* sp,
-                 const uint32_t* pr, bool big, std::vector<int32_t>& nch, std::vector<cld_chunk>& ch) -> int {
+  auto sub = [&](const Batch& sb, bool big, std::vector<int32_t>& nch, std::vector<cld_chunk>& ch) -> int {
+    const uint64_t* o = sb.offs;
+    const size_t m = sb.n;
+    const uint8_t* sp = sb.special;
+    const uint32_t* pr = sb.priors;
     const uint64_t base = o[0], bytes = o[m] - base;
     pool_off.assign(m + 1, 0);
     for (size_t i = 0; i < m; ++i) {
       const uint64_t len = o[i + 1] - o[i];
       pool_off[i + 1] = pool_off[i] + (big ? 8 * len + 256 : small_pool ? 1 : len + len / 4 + 8);
     }
-    if (grow(&V.in, &V.in_cap, std::max<size_t>(bytes, 1)) || grow(&V.offs, &V.offs_cap, m + 1) ||
-        grow(&V.out, &V.out_cap, m) || grow(&V.pool, &V.pool_cap, pool_off[m]) ||
-        grow(&V.pool_off, &V.pool_off_cap, m + 1) || grow(&V.nch, &V.nch_cap, m) || grow(&V.pos, &V.pos_cap, m))
+    if (V.in.reserve(std::max<size_t>(bytes, 1)) || V.offs.reserve(m + 1) || V.out.reserve(m) ||
+        V.pool.reserve(pool_off[m]) || V.pool_off.reserve(m + 1) || V.nch.reserve(m) || V.pos.reserve(m))
       return CLD_ENOMEM;
-    if (sp && grow(&V.sp, &V.sp_cap, m)) return CLD_ENOMEM;
-    if (pr && grow(&V.pri, &V.pri_cap, 16 * m)) return CLD_ENOMEM;
+    if (sp && V.sp.reserve(m)) return CLD_ENOMEM;
+    if (pr && V.pri.reserve(16 * m)) return CLD_ENOMEM;
     hipStream_t s = d->stream;
     HIP_OK(hipStreamWaitEvent(s, d->done, 0));
-    if (bytes) HIP_OK(hipMemcpyAsync(V.in, b + base, bytes, hipMemcpyHostToDevice, s));
+    if (bytes) HIP_OK(hipMemcpyAsync(V.in, sb.buf + base, bytes, hipMemcpyHostToDevice, s));
     HIP_OK(hipMemcpyAsync(V.offs, o, (m + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     HIP_OK(hipMemcpyAsync(V.pool_off, pool_off.data(), (m + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     if (sp) HIP_OK(hipMemcpyAsync(V.sp, sp, m, hipMemcpyHostToDevice, s));
@@ -1593,7 +1647,7 @@ int run_vec_shard(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n,
     // CLD_FLAG_CHECK_UTF8: the kernels get the prepared batch, in which a
     // rejected document is empty (a valid one is a copy: its chunk offsets
     // index the document as given either way)
-    const bool chk = (cflags & CLD_FLAG_CHECK_UTF8) != 0;
+    const bool chk = (b.flags & CLD_FLAG_CHECK_UTF8) != 0;
     const uint8_t* kb = V.in - base;
     const uint64_t* ko = V.offs;
     uint64_t kbase = base;
@@ -1604,8 +1658,7 @@ int run_vec_shard(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n,
       kbase = 0;
     }
     {
-      if (grow(&d->d_requeue, &d->requeue_cap, m) || grow(&d->d_requeue2, &d->requeue2_cap, m) ||
-          grow(&d->d_lsorted, &d->lsorted_cap, m) || grow(&d->d_lkey, &d->lkey_cap, m))
+      if (d->d_requeue.reserve(m) || d->d_requeue2.reserve(m) || d->d_lsorted.reserve(m) || d->d_lkey.reserve(m))
         return CLD_ENOMEM;
       // HTML pages: rewritten into plain text with each byte's page offset
       // (cld_html.hip), then scored by k_long<VEC> like plain documents
@@ -1614,9 +1667,8 @@ int run_vec_shard(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n,
       const uint32_t* hpz = nullptr;
       const uint32_t* hgz = nullptr;
       if (sp) {
-        if (grow(&d->d_hbuf, &d->hbuf_cap, std::max<size_t>(bytes, 1)) ||
-            grow(&d->d_hflag, &d->hflag_cap, std::max<size_t>(bytes, 1)) ||
-            grow(&d->d_hpos, &d->hpos_cap, 2 * std::max<size_t>(bytes, 1)))
+        const size_t hb_bytes = std::max<size_t>(bytes, 1);
+        if (d->d_hbuf.reserve(hb_bytes) || d->d_hflag.reserve(hb_bytes) || d->d_hpos.reserve(2 * hb_bytes))
           return CLD_ENOMEM;
         hb = d->d_hbuf - kbase;
         hf = d->d_hflag - kbase;
@@ -1629,7 +1681,7 @@ int run_vec_shard(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n,
       HIP_OK(cld_launch_route_vec((int)m, d->d_counters, d->d_requeue, s));
       HIP_OK(cld_launch_order_long(ko, d->d_requeue, d->d_counters, d->d_lkey, d->d_lhist, d->d_lsorted, false, s));
       HIP_OK(cld_launch_long_vec(d->d_T, kb, ko, d->d_lsorted, V.out, d->d_slots, V.vslots, d->n_slots,
-                                 d->d_requeue2, d->d_counters, cflags & kCldFlags, sp ? V.sp : nullptr, pr ? V.pri : nullptr, hb, hf,
+                                 d->d_requeue2, d->d_counters, b.flags & kCldFlags, sp ? V.sp : nullptr, pr ? V.pri : nullptr, hb, hf,
                                  hpz, hgz, V.pool, V.pool_off, V.nch, s));
       if (chk) {
         if (int rc = enqueue_fixup(d, V.out, m, s, V.nch)) return rc;
@@ -1638,7 +1690,7 @@ int run_vec_shard(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n,
     nch.resize(m);
     uint32_t ctr[kCtrSlots];
     HIP_OK(hipMemcpyAsync(ctr, d->d_counters, sizeof(ctr), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(res, V.out, m * sizeof(cld_result), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(sb.out, V.out, m * sizeof(cld_result), hipMemcpyDeviceToHost, s));
     HIP_OK(hipMemcpyAsync(nch.data(), V.nch, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
     // statistics (cld_last_batch_stats): documents the parallel span builder
@@ -1654,7 +1706,7 @@ int run_vec_shard(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n,
       pos[i] = total;
       if (nch[i] > 0) total += (uint64_t)nch[i];
     }
-    if (grow(&V.compact, &V.compact_cap, std::max<uint64_t>(total, 1))) return CLD_ENOMEM;
+    if (V.compact.reserve(std::max<uint64_t>(total, 1))) return CLD_ENOMEM;
     HIP_OK(hipMemcpyAsync(V.pos, pos.data(), m * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     HIP_OK(cld_launch_vec_gather(V.pool, V.pool_off, V.nch, V.pos, (int)m, V.compact, s));   // (-1: no chunks)
     ch.resize(total);
@@ -1665,13 +1717,13 @@ int run_vec_shard(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n,
   };
   size_t a = 0;
   bool failed = false;
-  while (a < n) {
+  while (a < b.n) {
     size_t m = 1;                                       // at least one document, then up to the limits
-    while (a + m < n && m < kSub && offs[a + m + 1] - offs[a] <= kSubBytes) ++m;
+    while (a + m < b.n && m < kSub && b.offs[a + m + 1] - b.offs[a] <= kSubBytes) ++m;
+    const Batch sb = b.slice(a, m);
     std::vector<int32_t> nch;
     std::vector<cld_chunk> ch;
-    if (int rc = sub(buf, offs + a, m, out + a, special ? special + a : nullptr, priors ? priors + 16 * a : nullptr,
-                     false, nch, ch)) {
+    if (int rc = sub(sb, false, nch, ch)) {
       if (rc == CLD_ENOMEM && m > 1 && kSubBytes > (1u << 20)) {   // smaller sub-batches, same documents
         kSubBytes /= 2;
         continue;
@@ -1684,27 +1736,16 @@ int run_vec_shard(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n,
     for (size_t i = 0; i < m; ++i)
       if (nch[i] < 0) bad.push_back(i);
     if (!bad.empty()) {
-      std::vector<uint8_t> rb, rsp;
-      std::vector<uint64_t> ro{0};
-      std::vector<uint32_t> rpr;
-      for (size_t i : bad) {
-        rb.insert(rb.end(), buf + offs[a + i], buf + offs[a + i + 1]);
-        ro.push_back(rb.size());
-        if (special) rsp.push_back(special[a + i]);
-        if (priors) rpr.insert(rpr.end(), priors + 16 * (a + i), priors + 16 * (a + i + 1));
-      }
-      std::vector<cld_result> rres(bad.size());
+      Gathered g(sb, bad);
       std::vector<int32_t> nch2;
       std::vector<cld_chunk> ch2;
-      if (int rc = sub(rb.empty() ? buf : rb.data(), ro.data(), bad.size(), rres.data(),
-                       special ? rsp.data() : nullptr, priors ? rpr.data() : nullptr, true, nch2, ch2))
-        return rc;
+      if (int rc = sub(g.b, true, nch2, ch2)) return rc;
       std::vector<cld_chunk> merged;
       merged.reserve(ch.size() + ch2.size());
       size_t c1 = 0, c2 = 0, j = 0;
       for (size_t i = 0; i < m; ++i) {
         if (j < bad.size() && bad[j] == i) {
-          out[a + i] = rres[j];
+          sb.out[i] = g.out[j];
           const int32_t k = nch2[j];
           if (k < 0) failed = true;                   // no vector: an empty one, and CLD_EIO
           const size_t kk = k > 0 ? (size_t)k : 0;
@@ -1726,6 +1767,41 @@ int run_vec_shard(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n,
   d->last = vst;
   d->stats_pending = false;
   return failed ? CLD_EIO : CLD_OK;
+}
+
+// A device error of any shard wins over CLD_EIO (some documents without a
+// result, every other one complete).
+int first_error(const std::vector<int>& rcs) {
+  int partial = CLD_OK;
+  for (int r : rcs) {
+    if (r == CLD_EIO) partial = CLD_EIO;
+    else if (r) return r;
+  }
+  return partial;
+}
+
+// Multi-GPU fan-out of a batch: contiguous shards of equal estimated kernel
+// cost, cut at document boundaries (cld_plan_shards; one context: the whole
+// batch), run(k, shard) for every shard k that holds documents -- on this
+// thread when there is only one such shard, else on a thread each -- and the
+// shards' return codes folded by first_error.
+template <class RunShard>
+int fan_out(const Batch& b, RunShard run) {
+  const size_t ndev = g_devs.size();
+  std::vector<size_t> cut(ndev + 1, 0);
+  cut[ndev] = b.n;
+  if (ndev > 1) cld_plan_shards(b.offs, b.n, (int)ndev, cut.data());
+  size_t busy = 0;
+  for (size_t k = 0; k < ndev; ++k) busy += cut[k + 1] > cut[k];
+  std::vector<int> rcs(ndev, CLD_OK);
+  std::vector<std::thread> th;
+  for (size_t k = 0; k < ndev; ++k) {
+    if (cut[k + 1] == cut[k]) continue;
+    auto job = [&, k] { rcs[k] = run(k, b.slice(cut[k], cut[k + 1] - cut[k])); };
+    if (busy == 1) job(); else th.emplace_back(job);
+  }
+  for (auto& t : th) t.join();
+  return first_error(rcs);
 }
 
 // ------------------------------------------------ detect_language batching
@@ -1763,24 +1839,6 @@ int load_dynamic(const uint8_t* data, size_t len, const std::string& label) {
   return CLD_OK;
 }
 
-int swap_tables_all(const HostTables& nt) {
-  std::vector<StagedTables> st(g_devs.size());
-  for (size_t i = 0; i < g_devs.size(); ++i) {
-    std::lock_guard<std::mutex> dl(g_devs[i]->mu);
-    if (int rc = stage_tables(g_devs[i], nt, &st[i])) {
-      for (size_t j = 0; j <= i; ++j) discard_tables(g_devs[j], &st[j]);
-      fprintf(stderr, "cld_mi355x: table upload failed on device %d; the tables in use are kept\n", g_devs[i]->id);
-      return rc;
-    }
-  }
-  for (size_t i = 0; i < g_devs.size(); ++i) {       // cannot fail short of a device error
-    std::lock_guard<std::mutex> dl(g_devs[i]->mu);
-    if (int rc = commit_tables(g_devs[i], &st[i])) return rc;
-  }
-  return CLD_OK;
-}
-
-
 }  // namespace
 
 extern "C" {
@@ -1798,7 +1856,7 @@ int cld_init(const char* tables_path, int n_devices) {
     return g_init_rc = CLD_ENODEV;
   }
   if (n_devices <= 0 || n_devices > count) n_devices = count;
-  if (const char* e = getenv("CLD_MI355X_DEVICES")) n_devices = std::max(1, std::min(count, atoi(e)));
+  n_devices = std::max(1, std::min(count, (int)env_long("CLD_MI355X_DEVICES", n_devices)));
   std::vector<int> ids;
   for (int i = 0; i < n_devices; ++i) ids.push_back(i);
   // CLD_MI355X_DEVICE_MAP="0,0": one context per listed HIP ordinal, repeats
@@ -1820,8 +1878,7 @@ int cld_init(const char* tables_path, int n_devices) {
   // CLD_MI355X_CONTEXTS=k: k contexts per GPU (own streams, scratch and k_long
   // slots), so concurrent request-sized calls run side by side on one GPU
   // instead of queueing behind each other's longest document (pick_context)
-  int per = 1;
-  if (const char* e = getenv("CLD_MI355X_CONTEXTS")) per = std::max(1, std::min(64, atoi(e)));
+  const int per = std::max(1, std::min(64, (int)env_long("CLD_MI355X_CONTEXTS", 1)));
   for (int id : ids)
     for (int k = 0; k < per; ++k) {
       Device* d = new Device();
@@ -1918,76 +1975,12 @@ int cld_plan_shards(const uint64_t* offsets, size_t n, int nshards, size_t* cuts
 }
 
 namespace {
-void dl_stop();
-}
-void cld_shutdown(void) {
-  std::lock_guard<std::mutex> lk(g_init_mu);
-  std::unique_lock<std::shared_mutex> tl(g_swap_mu);
-  dl_stop();
-  for (Device* d : g_devs) {
-    (void)hipSetDevice(d->id);
-    (void)hipStreamSynchronize(d->stream);
-    (void)hipFree(d->d_blob); (void)hipFree((void*)d->T.cpt); (void)hipFree((void*)d->T.keytab); (void)hipFree((void*)d->T.compat.adds); (void)hipFree(d->d_T); (void)hipFree(d->d_arena); (void)hipFree(d->d_counters);
-    (void)hipFree(d->d_requeue); (void)hipFree(d->d_requeue2); (void)hipFree(d->d_lsorted); (void)hipFree(d->d_lkey); (void)hipFree(d->d_lhist); (void)hipFree(d->d_slots); (void)hipFree(d->d_buf); (void)hipFree(d->d_offs); (void)hipFree(d->d_out);
-    (void)hipFree(d->d_sbuf); (void)hipFree(d->d_soffs); (void)hipFree(d->d_sscr);
-    (void)hipFree(d->d_vp); (void)hipFree(d->d_cbuf); (void)hipFree(d->d_coffs);
-    (void)hipFree(d->d_hbuf); (void)hipFree(d->d_hflag); (void)hipFree(d->d_hpos);
-    (void)hipFree(d->d_spec_out); (void)hipFree(d->d_spec_take);
-    (void)hipFree(d->d_store); (void)hipFree(d->d_meta); (void)hipFree(d->d_stlists); (void)hipFree(d->d_parlists);
-    for (auto& t : d->ev_pool) for (auto& e : t) (void)hipEventDestroy(e);
-    for (auto& h : d->hs) {
-      (void)hipHostFree(h.h_in); (void)hipHostFree(h.h_offs); (void)hipHostFree(h.h_out);
-      (void)hipFree(h.d_in); (void)hipFree(h.d_offs); (void)hipFree(h.d_out);
-      (void)hipHostFree(h.h_sp); (void)hipHostFree(h.h_pri); (void)hipFree(h.d_sp); (void)hipFree(h.d_pri);
-      (void)hipHostFree(h.h_vp); (void)hipFree(h.d_vp);
-      (void)hipEventDestroy(h.up); (void)hipEventDestroy(h.comp); (void)hipEventDestroy(h.down);
-    }
-    (void)hipHostFree(d->h_ctr);
-    (void)hipFree(d->d_ctrs);
-    for (void* p : {(void*)d->vec.arena, (void*)d->vec.vslots, (void*)d->vec.in, (void*)d->vec.offs, (void*)d->vec.out, (void*)d->vec.sp,
-                    (void*)d->vec.pri, (void*)d->vec.pool, (void*)d->vec.pool_off, (void*)d->vec.nch,
-                    (void*)d->vec.pos, (void*)d->vec.order, (void*)d->vec.compact})
-      if (p) (void)hipFree(p);
-    for (TinySlot& t : d->tiny) {
-      if (t.s) (void)hipStreamSynchronize(t.s);
-      (void)hipHostFree(t.h); (void)hipFree(t.dv); (void)hipFree(t.d_rq);
-      if (t.s) (void)hipStreamDestroy(t.s);
-    }
-    (void)hipEventDestroy(d->done);
-    (void)hipStreamDestroy(d->up_stream);
-    (void)hipStreamDestroy(d->down_stream);
-    (void)hipStreamDestroy(d->stream);
-    delete d;
-  }
-  g_devs.clear();
-  g_tab = HostTables();
-  g_dynamic = false;
-  g_inited = false;
-  g_ready.store(false, std::memory_order_release);
-  g_init_rc = CLD_ENODEV;
-}
-
-namespace {
-// A device error of any shard wins over CLD_EIO (some documents without a
-// result, every other one complete).
-int first_error(const std::vector<int>& rcs) {
-  int partial = CLD_OK;
-  for (int r : rcs) {
-    if (r == CLD_EIO) partial = CLD_EIO;
-    else if (r) return r;
-  }
-  return partial;
-}
-}  // namespace
-
-namespace {
 // Batches below this much text (CLD_SMALL_BATCH_MB, default 16) run whole on
 // one context -- the least busy one -- instead of being split across all of
 // them: a request-sized batch gains nothing from a split (its time is its
 // longest document's), and concurrent callers then each get a context.
 uint64_t small_batch_bytes() {
-  static const uint64_t v = (getenv("CLD_SMALL_BATCH_MB") ? strtoull(getenv("CLD_SMALL_BATCH_MB"), nullptr, 10) : 16ull)
-                            << 20;
+  static const uint64_t v = env_u64("CLD_SMALL_BATCH_MB", 16) << 20;
   return v;
 }
 struct Picked {
@@ -1995,7 +1988,19 @@ struct Picked {
   explicit Picked(Device* x) : d(x) { d->inflight.fetch_add(1); }
   ~Picked() { d->inflight.fetch_sub(1); }
 };
-Device* pick_context();
+Device* pick_context() {
+  static std::atomic<unsigned> rr{0};
+  const size_t n = g_devs.size();
+  const unsigned start = rr.fetch_add(1);
+  Device* best = g_devs[start % n];
+  int bl = best->inflight.load();
+  for (size_t i = 1; i < n && bl > 0; ++i) {
+    Device* d = g_devs[(start + i) % n];
+    const int l = d->inflight.load();
+    if (l < bl) { bl = l; best = d; }
+  }
+  return best;
+}
 
 // Request coalescing (cld_detect_batch below small_batch_bytes()).  A launch
 // lasts as long as its longest document (one wavefront scores it start to
@@ -2011,15 +2016,12 @@ constexpr uint64_t kCoalesceBytes = 64ull << 20;
 constexpr size_t kCoalesceDocs = 256 * 1024;
 using cld::CoReq;
 bool tiny_request(const uint64_t* offs, size_t n, uint32_t flags) {
-  if (n > kTinyDocs || (flags & kPrepFlags) || !tiny_enabled()) return false;
-  uint64_t bad = 0;
-  for (size_t i = 0; i < n; ++i) bad |= (uint64_t)(offs[i + 1] - offs[i] > (uint64_t)kWaveCap);
-  return bad == 0;
+  return n <= kTinyDocs && !(flags & kPrepFlags) && tiny_enabled() && all_fit_wave(offs, n);
 }
 struct Arena {                  // pinned staging of one dispatch (reused)
-  uint8_t* buf = nullptr; size_t buf_cap = 0;
-  uint64_t* offs = nullptr; size_t offs_cap = 0;
-  cld_result* out = nullptr; size_t out_cap = 0;
+  PinBuf<uint8_t> buf;
+  PinBuf<uint64_t> offs;
+  PinBuf<cld_result> out;
 };
 std::mutex g_arena_mu;
 std::vector<Arena*> g_arenas;   // free arenas
@@ -2028,7 +2030,7 @@ void run_group(const std::vector<CoReq*>& grp, void*) {
   if (grp.size() == 1) {        // nothing to merge: straight from the caller's buffers
     CoReq* r = grp[0];
     Picked p(pick_context());
-    r->rc = run_host_shard_isolating(p.d, r->buf, r->offs, r->n, (cld_result*)r->out, r->flags);
+    r->rc = run_host_shard_isolating(p.d, Batch{r->buf, r->offs, r->n, (cld_result*)r->out, r->flags});
     return;
   }
   Arena* a = nullptr;
@@ -2041,8 +2043,7 @@ void run_group(const std::vector<CoReq*>& grp, void*) {
   uint64_t bytes = 0;
   for (CoReq* r : grp) { docs += r->n; bytes += r->offs[r->n] - r->offs[0]; }
   int rc = CLD_OK;
-  if (grow_host(&a->buf, &a->buf_cap, std::max<uint64_t>(bytes, 1)) || grow_host(&a->offs, &a->offs_cap, docs + 1) ||
-      grow_host(&a->out, &a->out_cap, docs))
+  if (a->buf.reserve(std::max<uint64_t>(bytes, 1)) || a->offs.reserve(docs + 1) || a->out.reserve(docs))
     rc = CLD_ENOMEM;
   if (rc == CLD_OK) {
     size_t k = 0;
@@ -2056,7 +2057,7 @@ void run_group(const std::vector<CoReq*>& grp, void*) {
     }
     a->offs[docs] = at;
     Picked p(pick_context());
-    rc = run_host_shard_isolating(p.d, a->buf, a->offs, docs, a->out, grp[0]->flags);
+    rc = run_host_shard_isolating(p.d, Batch{a->buf, a->offs, docs, a->out, grp[0]->flags});
   }
   size_t k = 0;
   for (CoReq* r : grp) {
@@ -2090,7 +2091,7 @@ cld::Coalescer* coalescer() {
     x->tiny_docs = kTinyDocs;
     x->max_bytes = kCoalesceBytes;
     x->max_docs = kCoalesceDocs;
-    x->spin_us = getenv("CLD_COALESCE_SPIN_US") ? atoi(getenv("CLD_COALESCE_SPIN_US")) : 0;
+    x->spin_us = (int)env_long("CLD_COALESCE_SPIN_US", 0);
     // the dispatcher wakes every member itself (CLD_COALESCE_WAKE=tree: members
     // wake each other): 256 callers 146K -> 263K docs/s, p99 74 -> 20 ms (r5d)
     x->tree_wake = getenv("CLD_COALESCE_WAKE") && !strcmp(getenv("CLD_COALESCE_WAKE"), "tree");
@@ -2119,20 +2120,20 @@ int run_coalesced(const uint8_t* buf, const uint64_t* offs, size_t n, cld_result
 // once a call with no other in flight runs on its caller's thread (dl_direct).
 cld::DlQueue g_dlq;
 int dl_dispatchers() {
-  static const int v = std::max(1, std::min(tiny_slots(), getenv("CLD_DL_DISPATCHERS") ? atoi(getenv("CLD_DL_DISPATCHERS")) : 4));
+  static const int v = std::max(1, std::min(tiny_slots(), (int)env_long("CLD_DL_DISPATCHERS", 4)));
   return v;
 }
 bool dl_queue_on() {
-  static const bool v = !(getenv("CLD_DL_QUEUE") && atoi(getenv("CLD_DL_QUEUE")) == 0);
+  static const bool v = env_long("CLD_DL_QUEUE", 1) != 0;
   return v;
 }
 // how long callers (while fewer than 16 calls are in flight) and idle dispatchers spin before sleeping
 int dl_caller_spin_us() {
-  static const int v = getenv("CLD_DL_SPIN_US") ? atoi(getenv("CLD_DL_SPIN_US")) : 30;
+  static const int v = (int)env_long("CLD_DL_SPIN_US", 30);
   return v;
 }
 int dl_dispatcher_spin_us() {
-  static const int v = getenv("CLD_DL_IDLE_SPIN_US") ? atoi(getenv("CLD_DL_IDLE_SPIN_US")) : 100;
+  static const int v = (int)env_long("CLD_DL_IDLE_SPIN_US", 100);
   return v;
 }
 
@@ -2150,19 +2151,12 @@ void dl_dispatch(Device* d, int k) {
       const size_t n = std::min(kTinyDocs, v.size() - a);
       cld::DlReq* const* g = v.data() + a;
       auto doc = [&](size_t i) { return DocRef{g[i]->p, g[i]->len}; };
-      int rc;
-      {
-        std::lock_guard<std::mutex> lk(t->mu);
-        rc = tiny_run_slot(d, t, n, doc, out.data(), 0);
-      }
-      if (rc == CLD_OK) {
-        cld_batch_stats st{};
-        rc = tiny_redo_requeued(d, n, doc, out.data(), 0, &st);
-      }
+      cld_batch_stats st{};
+      t->mu.lock();
+      const int rc = tiny_call(d, t, n, doc, out.data(), 0, &st);
       for (size_t i = 0; i < n; ++i) {
         *static_cast<cld_result*>(g[i]->res) = out[i];
-        // a document without a result is redone alone by its caller
-        g[i]->rc = rc == kDocsFailed ? (out[i].summary_lang == CLD_LANG_FAILED ? kDocsFailed : CLD_OK) : rc;
+        g[i]->rc = tiny_doc_rc(rc, out[i]);
         g_dlq.done_one();
       }
       cld::finish_batch(g, n);
@@ -2180,16 +2174,10 @@ void dl_dispatch(Device* d, int k) {
 bool dl_direct(const char* t, size_t len, cld_result* res, int* rc) {
   Device* d = g_devs[0];
   for (int k = 0; k < dl_dispatchers(); ++k) {
-    std::unique_lock<std::mutex> lk(d->tiny[k].mu, std::try_to_lock);
-    if (!lk.owns_lock()) continue;
+    if (!d->tiny[k].mu.try_lock()) continue;
+    cld_batch_stats st{};
     auto doc = [&](size_t) { return DocRef{(const uint8_t*)t, len}; };
-    int r = tiny_run_slot(d, &d->tiny[k], 1, doc, res, 0);
-    lk.unlock();
-    if (r == CLD_OK) {
-      cld_batch_stats st{};
-      r = tiny_redo_requeued(d, 1, doc, res, 0, &st);
-    }
-    *rc = r == kDocsFailed ? (res->summary_lang == CLD_LANG_FAILED ? kDocsFailed : CLD_OK) : r;
+    *rc = tiny_doc_rc(tiny_call(d, &d->tiny[k], 1, doc, res, 0, &st), *res);
     return true;
   }
   return false;
@@ -2211,8 +2199,7 @@ bool dl_queue_takes(size_t len) {
     st = g_dl_state.load();
     if (st == 0) {
       bool ok = true;
-      for (Device* d : g_devs)
-        if (d->d_dbg || d->h_trace || d->d_prof || d->fault_doc != 0xFFFFFFFFu) ok = false;
+      for (Device* d : g_devs) ok &= !d->diagnostics();
       if (ok) {
         for (Device* d : g_devs)
           for (int k = 0; k < dl_dispatchers(); ++k) std::thread(dl_dispatch, d, k).detach();
@@ -2241,57 +2228,33 @@ void dl_stop() {
   g_dl_state.store(0);
 }
 
-Device* pick_context() {
-  static std::atomic<unsigned> rr{0};
-  const size_t n = g_devs.size();
-  const unsigned start = rr.fetch_add(1);
-  Device* best = g_devs[start % n];
-  int bl = best->inflight.load();
-  for (size_t i = 1; i < n && bl > 0; ++i) {
-    Device* d = g_devs[(start + i) % n];
-    const int l = d->inflight.load();
-    if (l < bl) { bl = l; best = d; }
-  }
-  return best;
-}
 }  // namespace
 
-namespace {
-// The checked entries report positions as int32 (valid_prefix_bytes is an int
-// in the reference): no document may be longer than INT32_MAX.
-bool docs_fit_int32(const uint64_t* offsets, size_t n) {
-  uint64_t bad = 0;
-  for (size_t i = 0; i < n; ++i) bad |= (uint64_t)(offsets[i + 1] - offsets[i] > 0x7FFFFFFFull);
-  return bad == 0;
+void cld_shutdown(void) {
+  std::lock_guard<std::mutex> lk(g_init_mu);
+  std::unique_lock<std::shared_mutex> tl(g_swap_mu);
+  dl_stop();
+  for (Device* d : g_devs) delete d;   // ~Device: drain, then free, then destroy
+  g_devs.clear();
+  g_tab = HostTables();
+  g_dynamic = false;
+  g_inited = false;
+  g_ready.store(false, std::memory_order_release);
+  g_init_rc = CLD_ENODEV;
 }
-}  // namespace
 
 int cld_detect_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, cld_result* out, uint32_t flags) {
-  if ((flags & ~(kPrepFlags | kPublicFlags)) != 0 || (n > 0 && (!buf || !offsets || !out))) return CLD_EINVAL;
+  if ((flags & ~(kPrepFlags | kPublicFlags)) != 0) return CLD_EINVAL;
+  if (int rc = check_batch(buf, offsets, n, out)) return rc;
   if (n == 0) return CLD_OK;
-  if (n > 0x7FFFFFFFu) return CLD_EINVAL;
-  if (!offsets_nondecreasing(offsets, n)) return CLD_EINVAL;
   if ((flags & CLD_FLAG_CHECK_UTF8) && !docs_fit_int32(offsets, n)) return CLD_EINVAL;
   int rc = cld_init(nullptr, 0);
   if (rc) return rc;
   std::shared_lock<std::shared_mutex> tl(g_swap_mu);
-  const size_t ndev = g_devs.size();
   if (offsets[n] - offsets[0] < small_batch_bytes()) return run_coalesced(buf, offsets, n, out, flags);
-  if (ndev == 1) return run_host_shard_isolating(g_devs[0], buf, offsets, n, out, flags);
-  // Shard by estimated kernel cost at document boundaries (cld_plan_shards).
-  std::vector<size_t> cut(ndev + 1, 0);
-  cld_plan_shards(offsets, n, (int)ndev, cut.data());
-  FanoutReg reg(ndev, buf, offsets, n, out);
-  std::vector<int> rcs(ndev, CLD_OK);
-  std::vector<std::thread> th;
-  for (size_t k = 0; k < ndev; ++k) {
-    if (cut[k + 1] == cut[k]) continue;
-    th.emplace_back([&, k] {
-      rcs[k] = run_host_shard_isolating(g_devs[k], buf, offsets + cut[k], cut[k + 1] - cut[k], out + cut[k], flags);
-    });
-  }
-  for (auto& t : th) t.join();
-  return first_error(rcs);
+  const Batch b{buf, offsets, n, out, flags};
+  FanoutReg reg(g_devs.size(), buf, offsets, n, out);
+  return fan_out(b, [&](size_t k, const Batch& s) { return run_host_shard_isolating(g_devs[k], s); });
 }
 
 int cld_hint_priors(const uint8_t* doc, size_t len, int is_plain_text, const cld_hints* hints, int16_t* priors14,
@@ -2352,12 +2315,6 @@ int apply_hints(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld
   return CLD_OK;
 }
 
-int check_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, const void* out) {
-  if (n > 0 && (!buf || !offsets || !out)) return CLD_EINVAL;
-  if (n > 0x7FFFFFFFu) return CLD_EINVAL;
-  if (!offsets_nondecreasing(offsets, n)) return CLD_EINVAL;
-  return CLD_OK;
-}
 }  // namespace
 
 // cld_detect_batch_ex, and with vp (n entries) cld_detect_batch_checked: the
@@ -2376,29 +2333,14 @@ static int detect_batch_ex(const uint8_t* buf, const uint64_t* offsets, size_t n
   std::vector<uint32_t> priors;
   const bool html = (flags & CLD_FLAG_HTML) != 0;
   if ((rc = apply_hints(buf, offsets, n, hints, html, &special, &priors))) return rc;
-  const uint8_t* sp = (html || !priors.empty()) ? special.data() : nullptr;
-  const uint32_t* pr = priors.empty() ? nullptr : priors.data();
-  const size_t ndev = g_devs.size();
-  if (ndev == 1) return run_host_shard_isolating(g_devs[0], buf, offsets, n, out, cf, sp, pr, html, vp);
-  if (offsets[n] - offsets[0] < small_batch_bytes()) {
+  const Batch b{buf, offsets, n, out, cf, (html || !priors.empty()) ? special.data() : nullptr,
+                priors.empty() ? nullptr : priors.data(), html, vp};
+  if (g_devs.size() > 1 && offsets[n] - offsets[0] < small_batch_bytes()) {
     Picked p(pick_context());
-    return run_host_shard_isolating(p.d, buf, offsets, n, out, cf, sp, pr, html, vp);
+    return run_host_shard_isolating(p.d, b);
   }
-  std::vector<size_t> cut(ndev + 1, 0);
-  cld_plan_shards(offsets, n, (int)ndev, cut.data());
-  FanoutReg reg(ndev, buf, offsets, n, out);
-  std::vector<int> rcs(ndev, CLD_OK);
-  std::vector<std::thread> th;
-  for (size_t k = 0; k < ndev; ++k) {
-    if (cut[k + 1] == cut[k]) continue;
-    th.emplace_back([&, k] {
-      rcs[k] = run_host_shard_isolating(g_devs[k], buf, offsets + cut[k], cut[k + 1] - cut[k], out + cut[k], cf,
-                              sp ? sp + cut[k] : nullptr, pr ? pr + 16 * cut[k] : nullptr, html,
-                              vp ? vp + cut[k] : nullptr);
-    });
-  }
-  for (auto& t : th) t.join();
-  return first_error(rcs);
+  FanoutReg reg(g_devs.size(), buf, offsets, n, out);
+  return fan_out(b, [&](size_t k, const Batch& s) { return run_host_shard_isolating(g_devs[k], s); });
 }
 
 extern "C" {
@@ -2459,9 +2401,8 @@ int cld_valid_prefix_batch(const uint8_t* buf, const uint64_t* offsets, size_t n
     size_t m = 1;
     while (a + m < n && m < kPieceDocs && offsets[a + m + 1] - offsets[a] <= kPieceBytes) ++m;
     const uint64_t base = offsets[a], bytes = offsets[a + m] - base;
-    if (grow(&d->d_buf, &d->buf_cap, std::max<size_t>(bytes, 1))) return CLD_ENOMEM;
-    if (grow(&d->d_offs, &d->offs_cap, m + 1)) return CLD_ENOMEM;
-    if (grow(&d->d_vp, &d->vp_cap, m)) return CLD_ENOMEM;
+    if (d->d_buf.reserve(std::max<size_t>(bytes, 1)) || d->d_offs.reserve(m + 1) || d->d_vp.reserve(m))
+      return CLD_ENOMEM;
     if (bytes) HIP_OK(hipMemcpyAsync(d->d_buf, buf + base, bytes, hipMemcpyHostToDevice, d->stream));
     HIP_OK(hipMemcpyAsync(d->d_offs, offsets + a, (m + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, d->stream));
     // (the offsets go up as the caller wrote them: the buffer base is biased instead)
@@ -2489,31 +2430,14 @@ int cld_detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t n, 
   std::vector<uint32_t> priors;
   const bool html = (flags & CLD_FLAG_HTML) != 0;
   if ((rc = apply_hints(buf, offsets, n, hints, html, &special, &priors))) return rc;
-  const uint8_t* sp = (html || !priors.empty()) ? special.data() : nullptr;
-  const uint32_t* pr = priors.empty() ? nullptr : priors.data();
+  const Batch b{buf, offsets, n, out, flags & (kCldFlags | CLD_FLAG_CHECK_UTF8),
+                (html || !priors.empty()) ? special.data() : nullptr, priors.empty() ? nullptr : priors.data(), html};
   const size_t ndev = g_devs.size();
-  std::vector<size_t> cut(ndev + 1, 0);
-  cut[1] = n;
-  if (ndev > 1) cld_plan_shards(offsets, n, (int)ndev, cut.data());
   std::vector<std::vector<cld_chunk>> vs(ndev);
   std::vector<std::vector<int32_t>> cs(ndev);
-  std::vector<int> rcs(ndev, CLD_OK);
-  std::vector<std::thread> th;
-  for (size_t k = 0; k < ndev; ++k) {
-    if (cut[k + 1] == cut[k]) continue;
-    auto job = [&, k] {
-      rcs[k] = run_vec_shard(g_devs[k], buf, offsets + cut[k], cut[k + 1] - cut[k], out + cut[k],
-                             sp ? sp + cut[k] : nullptr, pr ? pr + 16 * cut[k] : nullptr, &vs[k], &cs[k],
-                             flags & (kCldFlags | CLD_FLAG_CHECK_UTF8));
-    };
-    if (ndev == 1) job(); else th.emplace_back(job);
-  }
-  for (auto& t : th) t.join();
-  int partial = CLD_OK;                 // CLD_EIO: some document got no vector; all others are complete
-  for (int r : rcs) {
-    if (r == CLD_EIO) partial = CLD_EIO;
-    else if (r) return r;
-  }
+  // CLD_EIO: some document got no vector; all others are complete
+  const int partial = fan_out(b, [&](size_t k, const Batch& s) { return run_vec_shard(g_devs[k], s, &vs[k], &cs[k]); });
+  if (partial != CLD_OK && partial != CLD_EIO) return partial;
   size_t i = 0;
   uint64_t total = 0;
   for (size_t k = 0; k < ndev; ++k) {
@@ -2571,8 +2495,7 @@ int cld_prepare_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, uin
   std::lock_guard<std::mutex> lk(d->mu);
   HIP_OK(hipSetDevice(d->id));
   const uint64_t base = offsets[0], bytes = offsets[n] - offsets[0];
-  if (grow(&d->d_buf, &d->buf_cap, std::max<size_t>(bytes, 1))) return CLD_ENOMEM;
-  if (grow(&d->d_offs, &d->offs_cap, n + 1)) return CLD_ENOMEM;
+  if (d->d_buf.reserve(std::max<size_t>(bytes, 1)) || d->d_offs.reserve(n + 1)) return CLD_ENOMEM;
   std::vector<uint64_t> rel(n + 1);
   for (size_t i = 0; i <= n; ++i) rel[i] = offsets[i] - base;
   if (bytes) HIP_OK(hipMemcpyAsync(d->d_buf, buf + base, bytes, hipMemcpyHostToDevice, d->stream));
@@ -2737,7 +2660,7 @@ const char* detect_language(const char* text) {
     std::shared_lock<std::shared_mutex> tl(g_swap_mu);
     Picked p(pick_context());
     res = cld_result{};
-    rc = run_host_shard_isolating(p.d, (const uint8_t*)t, offs, 1, &res, 0);
+    rc = run_host_shard_isolating(p.d, Batch{(const uint8_t*)t, offs, 1, &res});
   }
   std::shared_lock<std::shared_mutex> tl(g_swap_mu);
   if (rc == CLD_EIO && res.summary_lang == CLD_LANG_FAILED) {

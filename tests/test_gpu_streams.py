@@ -206,6 +206,87 @@ def test_streamed_chunks_reuse_slots_safely():
     assert "chunked ok" in r.stdout
 
 
+CYCLES = r'''
+import numpy as np
+import cld_amd, corpus
+from oracle import Oracle
+from test_gpu_html_hints import priors_for
+from test_gpu_parity import assert_same
+o = Oracle()
+tb, to = corpus.c2(300, seed=181)
+b2, o2 = corpus.c2(1980, seed=182)
+docs = [bytes(b2[o2[i]:o2[i + 1]]) for i in range(1980)]
+long_at = []
+for k, page in enumerate((4096, 8192, 12288, 16384)):          # 20 pages of 4-16 KB among the tweets
+    pb, po = corpus.c3(5, seed=183 + k, page=page)
+    for i in range(5):
+        long_at.append(97 * (5 * k + i) + 11 + len(long_at))
+        docs.insert(long_at[-1], bytes(pb[po[i]:po[i + 1]]))
+assert len(docs) == 2000 and all(len(docs[i]) >= 4096 for i in long_at)
+mb, mo = cld_amd.pack(docs)
+assert int(mo[-1]) < (1 << 20)                                   # one chunk even at CLD_CHUNK_MB=1, hence:
+rb, ro = cld_amd.pack(docs * 5)                                  # the same documents five times over: several chunks
+assert int(ro[-1]) > (2 << 20)
+sb, so = corpus.c3(100, seed=187, page=4096)                     # more long documents than the fused kernel takes whole
+vec_docs = [docs[i] for i in long_at] + [d for i, d in enumerate(docs) if i not in long_at][:44]
+chk_docs = docs[20:52]
+assert all(len(d) < 4096 for d in chk_docs)
+chk_docs[7] = ("naïve café " * 5).encode()[:-2]        # ends inside a two-byte character (its lead byte alone)
+hb, ho = corpus.html(8, seed=3)
+
+def flat(*arrays):
+    return b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)
+
+first = None
+for cycle in range(3):
+    cld_amd.init_device(0, cld_amd.SYNTH_TABLES)
+    tiny = cld_amd.detect_batch(buf=tb, offsets=to)
+    mixed = cld_amd.detect_batch(buf=mb, offsets=mo)
+    rep = cld_amd.detect_batch(buf=rb, offsets=ro)
+    staged = cld_amd.detect_batch(buf=sb, offsets=so)
+    vec = cld_amd.detect_batch_vec(docs=vec_docs)
+    chk, vp = cld_amd.detect_batch_checked(docs=chk_docs)
+    html = cld_amd.detect_batch_ex(buf=hb, offsets=ho, html=True)
+    assert [int(vp[i]) == len(d) for i, d in enumerate(chk_docs)] == [i != 7 for i in range(32)], vp
+    got = {"tiny": flat(tiny), "mixed": flat(mixed), "rep": flat(rep), "staged": flat(staged), "vec": flat(*vec),
+           "checked": flat(chk, vp), "html": flat(html)}
+    if cycle == 0:
+        first = got
+        assert_same(tiny, o.detect_batch(tb, to, threads=16), "tiny")
+        assert_same(mixed, o.detect_batch(mb, mo, threads=16), "mixed")
+        assert_same(rep, o.detect_batch(rb, ro, threads=16), "mixed x5")
+        assert_same(staged, o.detect_batch(sb, so, threads=16), "staged")
+        assert_same(html, o.detect_batch_ex(hb, ho, plain=np.zeros(8, np.uint8),
+                                            priors=priors_for(cld_amd, hb, ho, True, None), threads=8), "html")
+    for k in got:
+        assert got[k] == first[k], (cycle, k)
+    cld_amd.lib().cld_shutdown()
+print("cycles ok")
+'''
+
+
+def test_every_buffer_family_across_shutdown_cycles():
+    """Three times init_device / batches / cld_shutdown in one child process
+    (CLD_CHUNK_MB=1): every family of buffers a context owns is made, used and
+    released each cycle -- the tiny slots (300 tweets), the streamed chunk
+    slots with the fused long kernel (2,000 tweets with twenty 4-16 KB pages
+    among them; that batch is under 1 MB, one chunk, so it also runs five
+    times over as one batch of several chunks), the staged long path (100
+    4 KB pages: more long documents than go whole to the fused kernel), vector
+    mode (64 documents), the UTF-8 check (32 documents, one ending inside a
+    character) and the HTML rewrite (8 pages).  Every result array of cycles 2
+    and 3 equals cycle 1's byte for byte, and cycle 1's plain and HTML results
+    equal the oracle's.  Nothing is asserted about memory."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, CLD_CHUNK_MB="1",
+               PYTHONPATH=os.pathsep.join(os.path.join(root, p) for p in ("language-detector_amd", "oracle", "tests")))
+    r = subprocess.run([sys.executable, "-c", CYCLES], env=env, capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    assert "cycles ok" in r.stdout
+
+
 def test_tiny_batches_equal_the_oracle(gpu, oracle):
     """Request-sized batches of short documents take run_tiny (one upload, one
     k_wave launch, one download; cld_runtime.cpp).  Batches of 1..1024
