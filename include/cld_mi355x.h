@@ -288,6 +288,46 @@ int cld_detect_batch_device(int device, const uint8_t* d_buf, const uint64_t* d_
 int cld_detect_batch_device_ex(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
                                uint64_t buf_bytes, cld_result* d_out, uint32_t flags, void* stream);
 
+/* CLDHints (compact_lang_det.h:134-139) for callers whose hints live in device
+ * memory: no pointers. */
+typedef struct cld_hints_dev {
+  uint32_t content_language_off;  /* into the hint text buffer                              */
+  uint32_t content_language_len;  /* 0: none; read up to its first NUL, as strlen would;    */
+                                  /* a range past hint_text_bytes is clipped to the buffer  */
+  char     tld[4];                /* NUL-padded; tld[0] == 0: none; tld[3] != 0: ignored,   */
+                                  /* as the reference ignores a TLD longer than 3           */
+                                  /* (SetCLDTLDHint, compact_lang_det_hint_code.cc:1446)    */
+  int32_t  encoding_hint;         /* CLD_UNKNOWN_ENCODING for none                          */
+  int32_t  language_hint;         /* 26 for none                                            */
+} cld_hints_dev;                  /* 20 bytes */
+
+/* ApplyHints alone (compact_lang_det_impl.cc:1587-1684; cld_hint_priors for a
+ * batch in device memory, a GPU kernel: cld_hints.hip).  Every pointer in
+ * device memory of GPU `device`; asynchronous on `stream` (NULL: the
+ * runtime's); uses none of the context's scratch.  d_hints NULL: no hints.
+ * is_plain_text 0: the lang= scan of each document's first 8 KB.
+ * d_priors14 (14 per document, after TrimCLDLangPriors(4), zero-padded) and
+ * d_boosts16 (16 per document, as cld_hint_priors' boosts16): either may be
+ * NULL.  Bit-identical to cld_hint_priors on the same bytes and hints.
+ * CLD_EINVAL for tables without the hint sections; n == 0: CLD_OK. */
+int cld_hint_boosts_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                           const cld_hints_dev* d_hints, const uint8_t* d_hint_text,
+                           uint64_t hint_text_bytes, int is_plain_text,
+                           int16_t* d_priors14, uint32_t* d_boosts16, void* stream);
+
+/* cld_detect_batch_ex (ExtDetectLanguageSummary, compact_lang_det.h:324-335)
+ * for device-resident input: d_hints is NULL or one cld_hints_dev per
+ * document; flags = CLD_FLAG_HTML and the public CLD2 flags (debug flags
+ * ignored).  Preparation flags, CLD_FLAG_CHECK_UTF8 included, give
+ * CLD_EINVAL.  buf_bytes bounds d_offsets[n], as in
+ * cld_detect_batch_device_ex.  ApplyHints runs on the GPU in front of the
+ * scoring kernels; without hints and without CLD_FLAG_HTML the call is
+ * cld_detect_batch_device.  Asynchronous. */
+int cld_detect_batch_device_hints(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                                  uint64_t buf_bytes, const cld_hints_dev* d_hints,
+                                  const uint8_t* d_hint_text, uint64_t hint_text_bytes,
+                                  cld_result* d_out, uint32_t flags, void* stream);
+
 /* The preparation step alone, on GPU 0 (host buffers): out_buf receives the
  * prepared documents back to back (capacity >= offsets[n]-offsets[0] + n
  * bytes), out_offsets[0..n] their offsets.  flags: CLD_FLAG_STRIP_EXTRAS and/or

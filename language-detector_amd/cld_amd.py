@@ -50,7 +50,8 @@ EXPORTS = ("detect_language", "cld_init", "cld_init_device", "cld_shutdown", "cl
            "cld_detect_batch_device_ex", "cld_prepare_batch", "cld_host_alloc", "cld_host_free",
            "cld_kernel_times", "cld_detect_batch_ex", "cld_hint_priors", "cld_detect_batch_vec",
            "cld_detect_batch_checked", "cld_valid_prefix_host", "cld_valid_prefix_batch",
-           "cld_valid_prefix_device", "detect_language_checked")
+           "cld_valid_prefix_device", "detect_language_checked", "cld_hint_boosts_device",
+           "cld_detect_batch_device_hints")
 CHUNK_DTYPE = np.dtype([("offset", "<i4"), ("bytes", "<i4"), ("lang1", "<u2"), ("pad", "<u2")])   # cld_chunk
 
 
@@ -63,6 +64,37 @@ class Hints(ctypes.Structure):
     def make(cls, content_language=None, tld=None, encoding=UNKNOWN_ENCODING, language=UNKNOWN_LANGUAGE):
         enc = lambda v: v.encode() if isinstance(v, str) else v
         return cls(enc(content_language), enc(tld), encoding, language)
+
+
+# include/cld_mi355x.h cld_hints_dev: CLDHints without pointers, for hints that live in device memory
+HINTS_DEV_DTYPE = np.dtype([("content_language_off", "<u4"), ("content_language_len", "<u4"), ("tld", "S4"),
+                            ("encoding_hint", "<i4"), ("language_hint", "<i4")])
+assert HINTS_DEV_DTYPE.itemsize == 20
+
+
+def pack_hints(hints, n=None):
+    """list of Hints (None: no hint for that document) -> (HINTS_DEV_DTYPE[n], uint8 text):
+    the records cld_hint_boosts_device / cld_detect_batch_device_hints take, and the
+    buffer their content-language texts lie in, each followed by a NUL.  A TLD longer
+    than 3 bytes keeps its first 4, which marks it as ignored (as the reference ignores it)."""
+    if n is not None and len(hints) != n:
+        raise ValueError("need one Hints per document")
+    rec = np.zeros(len(hints), dtype=HINTS_DEV_DTYPE)
+    rec["encoding_hint"] = UNKNOWN_ENCODING
+    rec["language_hint"] = UNKNOWN_LANGUAGE
+    text = bytearray()
+    for i, h in enumerate(hints):
+        if h is None:
+            continue
+        cl = h.content_language_hint or b""
+        if cl:
+            rec["content_language_off"][i] = len(text)
+            rec["content_language_len"][i] = len(cl)
+            text += cl + b"\0"
+        rec["tld"][i] = (h.tld_hint or b"")[:4]
+        rec["encoding_hint"][i] = h.encoding_hint
+        rec["language_hint"][i] = h.language_hint
+    return rec, np.frombuffer(bytes(text), dtype=np.uint8)
 
 
 class BatchStats(ctypes.Structure):
@@ -141,6 +173,12 @@ def lib():
         L.cld_valid_prefix_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         L.cld_valid_prefix_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                               ctypes.c_void_p, ctypes.c_void_p]
+        L.cld_hint_boosts_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.cld_detect_batch_device_hints.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                    ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                    ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
         L.detect_language_checked.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
         L.detect_language_checked.restype = ctypes.c_char_p
         _lib = L
@@ -355,6 +393,27 @@ def detect_batch_device(device, d_buf_ptr, d_offsets_ptr, n, d_out_ptr, stream_p
     rc = lib().cld_detect_batch_device(device, d_buf_ptr, d_offsets_ptr, n, d_out_ptr, stream_ptr)
     if rc != 0:
         raise CldError("cld_detect_batch_device failed: %d" % rc)
+
+
+def hint_boosts_device(device, d_buf_ptr, d_offsets_ptr, n, d_hints_ptr=None, d_hint_text_ptr=None, hint_text_bytes=0,
+                       plain=True, d_priors14_ptr=None, d_boosts16_ptr=None, stream_ptr=None):
+    """cld_hint_boosts_device: ApplyHints as a GPU kernel, every pointer in device memory
+    (d_hints_ptr: HINTS_DEV_DTYPE records, see pack_hints); asynchronous on the stream.
+    d_priors14_ptr: int16[n, 14], d_boosts16_ptr: uint32[n, 16]; either may be None."""
+    rc = lib().cld_hint_boosts_device(device, d_buf_ptr, d_offsets_ptr, n, d_hints_ptr, d_hint_text_ptr,
+                                      hint_text_bytes, 1 if plain else 0, d_priors14_ptr, d_boosts16_ptr, stream_ptr)
+    if rc != 0:
+        raise CldError("cld_hint_boosts_device failed: %d" % rc)
+
+
+def detect_batch_device_hints(device, d_buf_ptr, d_offsets_ptr, n, buf_bytes, d_out_ptr, d_hints_ptr=None,
+                              d_hint_text_ptr=None, hint_text_bytes=0, flags=0, stream_ptr=None):
+    """cld_detect_batch_device_hints: detect_batch_ex for device-resident input.  flags:
+    FLAG_HTML, FLAG_SCORE_AS_QUADS, FLAG_BEST_EFFORT; asynchronous on the stream."""
+    rc = lib().cld_detect_batch_device_hints(device, d_buf_ptr, d_offsets_ptr, n, buf_bytes, d_hints_ptr,
+                                             d_hint_text_ptr, hint_text_bytes, d_out_ptr, flags, stream_ptr)
+    if rc != 0:
+        raise CldError("cld_detect_batch_device_hints failed: %d" % rc)
 
 
 def last_stats(device=0):

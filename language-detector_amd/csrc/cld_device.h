@@ -48,6 +48,24 @@ struct DevTables {
   uint32_t unknown_lang, english, tg_unknown, french, italian, german, spanish, hawaiian;
 };
 
+// What ApplyHints reads (cld_hints.hip), as device pointers into the same
+// blob: the sections cld::HintView views on the host.  langtag1 null: the blob
+// has no hint sections.
+struct DevHints {
+  const uint8_t* langtag1;    // CLDT_HINT_LANGTAG1: u32 n, cldt_hint_entry[n], string pool (keys end inside it)
+  const uint8_t* langtag2;
+  const uint8_t* tld;
+  const uint8_t* action;      // kLangCodeAction[256]
+  const uint8_t* remap;       // kLangCodeRemap[256]
+  const int16_t* enc;         // prior per Encoding value
+  const uint8_t* l2p;
+  const uint16_t* p2l_latn;
+  const uint16_t* p2l_othr;
+  const uint8_t* close_set;
+  uint32_t n_enc, l2p_size, n_langs;
+  uint32_t chinese, chinese_t, unknown_language;
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif

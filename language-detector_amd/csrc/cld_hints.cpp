@@ -1,4 +1,5 @@
-// cld_hints.cpp -- CLDHints -> prior boosts and whacks, on the host.
+// cld_hints.cpp -- CLDHints -> prior boosts and whacks, on the host: the
+// specification of ApplyHints in this project.
 //
 // Restates the reference's hint code (compact_lang_det_hint_code.cc) and the
 // prior half of ApplyHints (compact_lang_det_impl.cc:1524-1684) over tables
@@ -6,6 +7,12 @@
 // the kernels add to (boosts) or zero in (whacks) every chunk tote, exactly
 // where ScoreBoosts does (scoreonescriptspan.cc:125-152).  Pinned against the
 // reference's own hint code by tests/test_html_hints.py (oracle/refscan).
+//
+// The host entry points (cld_detect_batch_ex, _vec, _checked, cld_hint_priors)
+// run this code.  The device-resident ones (cld_detect_batch_device_hints,
+// cld_hint_boosts_device) run its restatement as a GPU kernel, cld_hints.hip,
+// which tests/test_gpu_device_hints.py holds to this file bit for bit: a
+// change of behaviour here has to be made there too.
 #include "cld_hints.h"
 
 #include <stdlib.h>

@@ -1,5 +1,6 @@
 // cld_hints.h -- host-side hint processing (CLDHints -> per-document prior
 // boosts / whacks), the runtime's restatement of the reference's hint code.
+// (The same stage as a GPU kernel, for device-resident input: cld_hints.hip.)
 #ifndef CLD_HINTS_H_
 #define CLD_HINTS_H_
 #include <stddef.h>

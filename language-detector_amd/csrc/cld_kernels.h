@@ -137,6 +137,16 @@ hipError_t cld_launch_valid_copy(const uint8_t* buf, const uint64_t* offs, int n
                                  uint8_t* out, uint64_t bytes_hint, hipStream_t s);
 hipError_t cld_launch_valid_fixup(const uint64_t* offs, int n, const int32_t* valid_prefix, cld_result* out,
                                   int32_t* n_chunks, uint32_t unknown_language, hipStream_t s);
+// ApplyHints (cld_hints.hip; compact_lang_det_impl.cc:1587-1684), one wave
+// per document: priors14 (14 per document, trimmed to 4, zero-padded),
+// boosts16 (the 16 langprobs enqueue() takes as `priors`) and special (the
+// routing byte: kSpecialHtml unless plain, kSpecialPriors when a langprob is
+// non-zero); each nullable.  hints (nullable): one record per document, its
+// content-language text in hint_text[0, hint_text_bytes).  plain 0: the lang=
+// scan of each document's first 8 KB.  H by value to the kernel.
+hipError_t cld_launch_apply_hints(const DevHints* H, const uint8_t* buf, const uint64_t* offs, int n,
+                                  const cld_hints_dev* hints, const uint8_t* hint_text, uint64_t hint_text_bytes,
+                                  int plain, int16_t* priors14, uint32_t* boosts16, uint8_t* special, hipStream_t s);
 // fault_doc (k_long): test hook, batch index of a document made to fail
 // (0xFFFFFFFF: none): it gets no result (summary CLD_LANG_FAILED).
 // seq_list (n entries, counters[kCtrRequeue2]): the documents k_long hands to

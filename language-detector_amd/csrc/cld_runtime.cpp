@@ -299,7 +299,7 @@ int parse_tables(HostTables* t, const std::string& label) {
       D.n_ent = (uint32_t)ent.size();
     }
   }
-  {  // optional hint sections (host only)
+  {  // optional hint sections: the host's views; device_hints() turns them into pointers into the uploaded blob
     cld::HintView& h = t->hints;
     h = cld::HintView();
     auto tbl = [&](uint32_t id) -> const uint8_t* {   // cldt_hint_entry table + pool, checked
@@ -388,6 +388,24 @@ DevTables device_tables(const DevTables& o, const uint8_t* d) {
   return T;
 }
 
+// The hint sections cld::HintView views in t.blob, as pointers into the blob's
+// copy at d (every field null / 0: the blob has no hint sections).
+DevHints device_hints(const HostTables& t, const uint8_t* d) {
+  DevHints H{};
+  const cld::HintView& v = t.hints;
+  if (!v.ok()) return H;
+  const uint8_t* b = t.blob.data();
+  auto dev = [&](const void* p) { return d + ((const uint8_t*)p - b); };
+  H.langtag1 = dev(v.langtag1); H.langtag2 = dev(v.langtag2); H.tld = dev(v.tld);
+  H.action = dev(v.action); H.remap = dev(v.remap);
+  H.enc = (const int16_t*)dev(v.enc); H.n_enc = v.n_enc;
+  H.l2p = dev(v.l2p); H.l2p_size = v.l2p_size;
+  H.p2l_latn = (const uint16_t*)dev(v.p2l_latn); H.p2l_othr = (const uint16_t*)dev(v.p2l_othr);
+  H.close_set = dev(v.close_set); H.n_langs = v.n_langs;
+  H.chinese = v.chinese; H.chinese_t = v.chinese_t; H.unknown_language = v.unknown_language;
+  return H;
+}
+
 // ------------------------------------------------------------ per-GPU context
 // Request-sized batches of short documents (run_tiny): at most kTinyDocs
 // documents of at most kWaveCap bytes.  One pinned block and its device twin
@@ -428,6 +446,7 @@ struct Device {
   size_t ev_used = 0;
   uint8_t* d_blob = nullptr;  // the table blob and T.cpt / keytab / compat.adds: commit_tables, drop_tables
   DevTables T{};
+  DevHints H{};               // the hint sections of d_blob (ApplyHints on the GPU, cld_hints.hip)
   DevBuf<DevTables> d_T;      // T in HBM (k_long reads the table set through a pointer)
   DevBuf<uint8_t> d_slots;    // k_long per-wave slots
   DevBuf<cld_result> d_spec_out;   // k_long's speculative pass-2 results (small batches; CLD_LONG_SPEC=0: off)
@@ -468,6 +487,10 @@ struct Device {
   DevBuf<uint32_t> d_hpos;      //   and (vec mode) each byte's page offset
   DevBuf<uint64_t> d_soffs;
   DevBuf<uint8_t> d_sscr;
+  // cld_detect_batch_device_hints: the routing bytes (k_html_rewrite updates them) and the 16 langprobs
+  // per document that the ApplyHints kernel leaves for enqueue()
+  DevBuf<uint8_t> d_hint_special;
+  DevBuf<uint32_t> d_hint_priors;
   // CLD_FLAG_CHECK_UTF8 (cld_valid.hip): valid prefixes, and the prepared batch in which a rejected
   // document is empty.  p_buf / p_offs: where enqueue_prepare left the prepared batch (d_sbuf or d_cbuf);
   // chk_offs / chk_vp: the offsets and prefixes the check ran on (enqueue_fixup reads them)
@@ -563,6 +586,7 @@ struct StagedTables {
   uint64_t* keytab = nullptr;
   uint64_t* adds = nullptr;
   DevTables T{};
+  DevHints H{};
 };
 
 int stage_tables(Device* d, const HostTables& t, StagedTables* st) {
@@ -570,6 +594,7 @@ int stage_tables(Device* d, const HostTables& t, StagedTables* st) {
   HIP_OK(hipMalloc(&st->blob, t.blob.size()));
   HIP_OK(hipMemcpy(st->blob, t.blob.data(), t.blob.size(), hipMemcpyHostToDevice));
   st->T = device_tables(t.offs, st->blob);
+  st->H = device_hints(t, st->blob);
   // per-character property table for the long-document kernel, built from the uploaded machines
   HIP_OK(hipMalloc(&st->cpt, cld_cpt_entries() * sizeof(uint64_t)));
   HIP_OK(cld_build_cpt(&st->T, st->cpt, d->stream));
@@ -600,6 +625,7 @@ void drop_tables(Device* d) {
   if (d->T.compat.adds) (void)hipFree((void*)d->T.compat.adds);
   d->d_blob = nullptr;
   d->T = DevTables{};
+  d->H = DevHints{};
 }
 
 // The caller holds d->mu or owns d exclusively.
@@ -609,6 +635,7 @@ int commit_tables(Device* d, StagedTables* st) {
   drop_tables(d);
   d->d_blob = st->blob;
   d->T = st->T;
+  d->H = st->H;
   *st = StagedTables();
   if (d->d_T.reserve(1)) return CLD_EFAULT;
   HIP_OK(hipMemcpy(d->d_T, &d->T, sizeof(DevTables), hipMemcpyHostToDevice));
@@ -2481,6 +2508,54 @@ int cld_detect_batch_device_ex(int device, const uint8_t* d_buf, const uint64_t*
   if ((rc = enqueue_prepare(d, d_buf, d_offsets, n, buf_bytes, flags, s))) return rc;
   if ((rc = enqueue(d, d->p_buf, d->p_offs, n, d_out, s, nullptr, nullptr, flags))) return rc;
   return (flags & CLD_FLAG_CHECK_UTF8) ? enqueue_fixup(d, d_out, n, s) : CLD_OK;
+}
+
+int cld_hint_boosts_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                           const cld_hints_dev* d_hints, const uint8_t* d_hint_text, uint64_t hint_text_bytes,
+                           int is_plain_text, int16_t* d_priors14, uint32_t* d_boosts16, void* stream) {
+  if (n > 0x7FFFFFFFu || (n > 0 && (!d_offsets || (!is_plain_text && !d_buf))) || (hint_text_bytes && !d_hint_text))
+    return CLD_EINVAL;
+  int rc = cld_init(nullptr, 0);
+  if (rc) return rc;
+  if (device < 0 || device >= (int)g_devs.size()) return CLD_EINVAL;
+  if (n == 0) return CLD_OK;
+  std::shared_lock<std::shared_mutex> tl(g_swap_mu);
+  Device* d = g_devs[device];
+  if (!d->H.langtag1) return CLD_EINVAL;            // tables without the hint sections
+  HIP_OK(hipSetDevice(d->id));
+  // (no scratch of the context is used: nothing to serialise with other batches)
+  HIP_OK(cld_launch_apply_hints(&d->H, d_buf, d_offsets, (int)n, d_hints, d_hint_text, hint_text_bytes,
+                                is_plain_text != 0, d_priors14, d_boosts16, nullptr,
+                                stream ? (hipStream_t)stream : d->stream));
+  return CLD_OK;
+}
+
+int cld_detect_batch_device_hints(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                                  uint64_t buf_bytes, const cld_hints_dev* d_hints, const uint8_t* d_hint_text,
+                                  uint64_t hint_text_bytes, cld_result* d_out, uint32_t flags, void* stream) {
+  if ((flags & ~(CLD_FLAG_HTML | kPublicFlags)) != 0 || n > 0x7FFFFFFFu || (hint_text_bytes && !d_hint_text) ||
+      (n > 0 && (!d_buf || !d_offsets || !d_out)))
+    return CLD_EINVAL;
+  int rc = cld_init(nullptr, 0);
+  if (rc) return rc;
+  if (device < 0 || device >= (int)g_devs.size()) return CLD_EINVAL;
+  if (n == 0) return CLD_OK;
+  std::shared_lock<std::shared_mutex> tl(g_swap_mu);
+  Device* d = g_devs[device];
+  std::lock_guard<std::mutex> lk(d->mu);
+  const bool html = (flags & CLD_FLAG_HTML) != 0;
+  if (html && !d->T.ent_names) return CLD_EINVAL;   // tables without the HTML sections
+  if ((html || d_hints) && !d->H.langtag1) return CLD_EINVAL;
+  HIP_OK(hipSetDevice(d->id));
+  hipStream_t s = stream ? (hipStream_t)stream : d->stream;
+  if (d->ev_used >= 4096) d->ev_used = 0;
+  if (!html && !d_hints) return enqueue(d, d_buf, d_offsets, n, d_out, s, nullptr, nullptr, flags);
+  if (d->d_hint_special.reserve(n) || d->d_hint_priors.reserve(16 * n)) return CLD_ENOMEM;
+  HIP_OK(hipStreamWaitEvent(s, d->done, 0));        // the previous batch may still read the two buffers
+  HIP_OK(cld_launch_apply_hints(&d->H, d_buf, d_offsets, (int)n, d_hints, d_hint_text, hint_text_bytes, !html,
+                                nullptr, d->d_hint_priors, d->d_hint_special, s));
+  // (the host never learns whether any document has a prior: the langprobs always go along)
+  return enqueue(d, d_buf, d_offsets, n, d_out, s, d->d_hint_special, d->d_hint_priors, flags, 0, html ? buf_bytes : 0);
 }
 
 int cld_prepare_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, uint32_t flags,
