@@ -328,6 +328,59 @@ int cld_detect_batch_device_hints(int device, const uint8_t* d_buf, const uint64
                                   const uint8_t* d_hint_text, uint64_t hint_text_bytes,
                                   cld_result* d_out, uint32_t flags, void* stream);
 
+/* cld_detect_batch_vec for device-resident input: every pointer is device
+ * memory of GPU `device`, the call is asynchronous on `stream` (NULL: the
+ * runtime's), nothing inside it waits for the GPU, and it returns once its
+ * kernels are enqueued.  d_out, d_chunk_offsets[0..n] and d_chunks are what
+ * cld_detect_batch_vec gives for the same documents, hints and flags.
+ *   flags        CLD_FLAG_HTML, the public CLD2 flags (debug flags ignored)
+ *                and CLD_FLAG_CHECK_UTF8; CLD_FLAG_STRIP_EXTRAS /
+ *                CLD_FLAG_CSTRING and unknown bits give CLD_EINVAL (chunk
+ *                offsets and prefixes index the documents as given).
+ *   d_hints      NULL or one cld_hints_dev per document (their texts in
+ *                d_hint_text); ApplyHints runs on the GPU, as in
+ *                cld_detect_batch_device_hints.
+ *   CHECK_UTF8   a rejected document gets the "rejected" result and an empty
+ *                vector; d_valid_prefix (NULL: not wanted; n entries)
+ *                receives SpanInterchangeValid per document, as
+ *                cld_detect_batch_checked gives it.  d_valid_prefix without
+ *                the flag is CLD_EINVAL.  The caller keeps documents
+ *                <= INT32_MAX bytes.
+ *   capacity     d_chunk_offsets always holds the true totals, d_chunks
+ *                receives the first chunk_cap chunks and nothing is written
+ *                past d_chunks + chunk_cap.  chunk_cap 0 with d_chunks NULL is
+ *                the sizing pass: read d_status->total_chunks, allocate, call
+ *                again.
+ *   buf_bytes    bounds d_offsets[n], as in cld_detect_batch_device_ex: it
+ *                sizes the working memory on the host (which never reads the
+ *                offsets).  CLD_ENOMEM, synchronously, if that does not fit.
+ *   big_regions  0: a document of len bytes builds its vector in a region of
+ *                len + len/4 + 8 chunks; else 8 len + 256, the two sizes
+ *                cld_detect_batch_vec uses.  That entry redoes a document
+ *                whose vector outgrows its region; here the host is not
+ *                asked, so such a document gets an empty vector, summary_lang
+ *                CLD_LANG_FAILED (lang3 UNKNOWN, zeros otherwise) and a count
+ *                in d_status->failed_docs, and every other document is
+ *                complete.  Redo those with big_regions = 1 or through
+ *                cld_detect_batch_vec.
+ * n == 0: CLD_OK, with d_chunk_offsets[0] = 0 and a zero status written where
+ * the pointers are not NULL.  n > 0x7FFFFFFF and tables without the HTML or
+ * hint sections (when asked for): CLD_EINVAL.  Calls enqueued back to back
+ * run one after another on the context's working memory.
+ * cld_last_batch_stats is not updated by this entry: nothing is read back. */
+typedef struct cld_vec_status {   /* 16 bytes, written by the last kernel of the call */
+  uint64_t total_chunks;          /* = d_chunk_offsets[n]; > chunk_cap means the CLD_ENOSPC case */
+  uint32_t failed_docs;           /* documents whose vector outgrew its pool region (above)    */
+  uint32_t rejected_docs;         /* CLD_FLAG_CHECK_UTF8: documents not interchange-valid      */
+} cld_vec_status;
+
+int cld_detect_batch_device_vec(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                                uint64_t buf_bytes, const cld_hints_dev* d_hints,
+                                const uint8_t* d_hint_text, uint64_t hint_text_bytes, uint32_t flags,
+                                int big_regions, cld_result* d_out, cld_chunk* d_chunks,
+                                uint64_t chunk_cap, uint64_t* d_chunk_offsets,
+                                int32_t* d_valid_prefix, cld_vec_status* d_status, void* stream);
+
 /* The preparation step alone, on GPU 0 (host buffers): out_buf receives the
  * prepared documents back to back (capacity >= offsets[n]-offsets[0] + n
  * bytes), out_offsets[0..n] their offsets.  flags: CLD_FLAG_STRIP_EXTRAS and/or

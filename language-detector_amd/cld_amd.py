@@ -51,7 +51,7 @@ EXPORTS = ("detect_language", "cld_init", "cld_init_device", "cld_shutdown", "cl
            "cld_kernel_times", "cld_detect_batch_ex", "cld_hint_priors", "cld_detect_batch_vec",
            "cld_detect_batch_checked", "cld_valid_prefix_host", "cld_valid_prefix_batch",
            "cld_valid_prefix_device", "detect_language_checked", "cld_hint_boosts_device",
-           "cld_detect_batch_device_hints")
+           "cld_detect_batch_device_hints", "cld_detect_batch_device_vec")
 CHUNK_DTYPE = np.dtype([("offset", "<i4"), ("bytes", "<i4"), ("lang1", "<u2"), ("pad", "<u2")])   # cld_chunk
 
 
@@ -70,6 +70,11 @@ class Hints(ctypes.Structure):
 HINTS_DEV_DTYPE = np.dtype([("content_language_off", "<u4"), ("content_language_len", "<u4"), ("tld", "S4"),
                             ("encoding_hint", "<i4"), ("language_hint", "<i4")])
 assert HINTS_DEV_DTYPE.itemsize == 20
+
+
+# include/cld_mi355x.h cld_vec_status: what cld_detect_batch_device_vec leaves in d_status
+VEC_STATUS_DTYPE = np.dtype([("total_chunks", "<u8"), ("failed_docs", "<u4"), ("rejected_docs", "<u4")])
+assert VEC_STATUS_DTYPE.itemsize == 16
 
 
 def pack_hints(hints, n=None):
@@ -179,6 +184,11 @@ def lib():
         L.cld_detect_batch_device_hints.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                                     ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                                     ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
+        L.cld_detect_batch_device_vec.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                  ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                  ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p]
         L.detect_language_checked.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
         L.detect_language_checked.restype = ctypes.c_char_p
         _lib = L
@@ -414,6 +424,24 @@ def detect_batch_device_hints(device, d_buf_ptr, d_offsets_ptr, n, buf_bytes, d_
                                              d_hint_text_ptr, hint_text_bytes, d_out_ptr, flags, stream_ptr)
     if rc != 0:
         raise CldError("cld_detect_batch_device_hints failed: %d" % rc)
+
+
+def detect_batch_device_vec(device, d_buf_ptr, d_offsets_ptr, n, buf_bytes, d_out_ptr, d_chunks_ptr, chunk_cap,
+                            d_chunk_offsets_ptr, d_status_ptr, d_hints_ptr=None, d_hint_text_ptr=None,
+                            hint_text_bytes=0, flags=0, big_regions=False, d_valid_prefix_ptr=None, stream_ptr=None):
+    """cld_detect_batch_device_vec: detect_batch_vec for device-resident input, asynchronous on
+    the stream.  d_out_ptr: RESULT_DTYPE[n], d_chunk_offsets_ptr: uint64[n + 1], d_status_ptr: one
+    VEC_STATUS_DTYPE record, d_chunks_ptr: CHUNK_DTYPE[chunk_cap] (None with chunk_cap 0: the
+    sizing pass -- read total_chunks from the status, allocate, call again).  flags: FLAG_HTML,
+    FLAG_CHECK_UTF8 (d_valid_prefix_ptr: int32[n] or None), FLAG_SCORE_AS_QUADS, FLAG_BEST_EFFORT.
+    Documents counted in failed_docs (summary_lang == LANG_FAILED, empty vector) are redone
+    with big_regions=True or through detect_batch_vec."""
+    rc = lib().cld_detect_batch_device_vec(device, d_buf_ptr, d_offsets_ptr, n, buf_bytes, d_hints_ptr,
+                                           d_hint_text_ptr, hint_text_bytes, flags, 1 if big_regions else 0,
+                                           d_out_ptr, d_chunks_ptr, chunk_cap, d_chunk_offsets_ptr,
+                                           d_valid_prefix_ptr, d_status_ptr, stream_ptr)
+    if rc != 0:
+        raise CldError("cld_detect_batch_device_vec failed: %d" % rc)
 
 
 def last_stats(device=0):

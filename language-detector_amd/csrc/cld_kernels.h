@@ -59,6 +59,28 @@ hipError_t cld_launch_long_vec(const DevTables* d_T, const uint8_t* buf, const u
                                cld_chunk* pool, const uint64_t* pool_off, int32_t* n_chunks, hipStream_t s);
 hipError_t cld_launch_vec_gather(const cld_chunk* pool, const uint64_t* pool_off, const int32_t* n_chunks,
                                  const uint64_t* pos, int n, cld_chunk* dst, hipStream_t s);
+// The device-resident vector path (cld_vec.hip; cld_detect_batch_device_vec),
+// the host steps of cld_detect_batch_vec as kernels:
+// cld_launch_vec_plan: region[i] = document i's pool region in chunks, for
+// cld_launch_scan_lengths to turn into pool_off -- len + len/4 + 8, with
+// kVecRegionsBig 8 len + 256, with kVecRegionsOne (the CLD_VEC_POOL_SMALL
+// test hook) 1.
+// cld_launch_vec_finish, after k_long<VEC> and the UTF-8 fixup: counts[i] =
+// max(n_chunks[i], 0) for the scan into the chunk offsets; a document with
+// n_chunks -1 gets the CLD_LANG_FAILED result and is counted in
+// status->failed_docs; valid_prefix (nullable; over offs, the documents as
+// given): documents the check rejected are counted in status->rejected_docs.
+// status is zeroed by the caller.
+// cld_launch_vec_gather_chunks: the first min(chunk_offs[n], cap) chunks from
+// the pool regions to dst in document order, work split over output
+// positions; writes status->total_chunks = chunk_offs[n].
+enum { kVecRegionsSmall = 0, kVecRegionsBig = 1, kVecRegionsOne = 2 };
+hipError_t cld_launch_vec_plan(const uint64_t* offs, int n, int mode, uint64_t* region, hipStream_t s);
+hipError_t cld_launch_vec_finish(const uint64_t* offs, int n, const int32_t* n_chunks, const int32_t* valid_prefix,
+                                 cld_result* out, uint32_t unknown_language, uint64_t* counts, cld_vec_status* status,
+                                 hipStream_t s);
+hipError_t cld_launch_vec_gather_chunks(const cld_chunk* pool, const uint64_t* pool_off, const uint64_t* chunk_offs,
+                                        int n, cld_chunk* dst, uint64_t cap, cld_vec_status* status, hipStream_t s);
 // special (nullable): per-document kSpecial* bits; HTML documents are appended
 // to special_list under counters[special_ctr] instead of being scored, hinted
 // ones (kSpecialPriors) are scored with their 16 ApplyHints langprobs

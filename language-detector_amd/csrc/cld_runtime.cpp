@@ -1618,6 +1618,15 @@ struct FanoutReg {
   }
 };
 
+// Test hook of both vector entries, read once per process: CLD_VEC_POOL_SMALL=1
+// makes the first-size pool regions one chunk each, so every multi-chunk
+// document outgrows its region (tests/test_gpu_vector.py: the host entry's
+// retry; tests/test_gpu_device_vec.py: the device entry's failed documents).
+bool vec_pool_small() {
+  static const bool v = env_long("CLD_VEC_POOL_SMALL", 0) > 0;
+  return v;
+}
+
 // ResultChunkVector mode on one device: documents in sub-batches (the
 // kernel is the exact sequential pipeline; no overlap needed), each
 // document building its vector in a pool region of len + len/4 + 8 chunks,
@@ -1638,9 +1647,7 @@ int run_vec_shard(Device* d, const Batch& b, std::vector<cld_chunk>* chunks, std
   const size_t kSub = 1024 * 1024;
   static const uint64_t kSubBytes0 = (uint64_t)env_long("CLD_VEC_SUB_MB", 256) << 20;
   uint64_t kSubBytes = kSubBytes0;   // halved while the device cannot hold a sub-batch's pool
-  // test hook: CLD_VEC_POOL_SMALL=1 makes first-pass pool regions too small so
-  // the retry below runs (tests/test_gpu_vector.py)
-  static const bool small_pool = env_long("CLD_VEC_POOL_SMALL", 0) > 0;
+  const bool small_pool = vec_pool_small();   // (test hook: every multi-chunk document takes the retry below)
   // One sub-batch: the documents of sb, document i building its vector in a
   // pool region of len + len/4 + 8 chunks (big: 8 len + 256); results to
   // sb.out, vector sizes to nch (-1: the document overflowed its pool region
@@ -2556,6 +2563,95 @@ int cld_detect_batch_device_hints(int device, const uint8_t* d_buf, const uint64
                                 nullptr, d->d_hint_priors, d->d_hint_special, s));
   // (the host never learns whether any document has a prior: the langprobs always go along)
   return enqueue(d, d_buf, d_offsets, n, d_out, s, d->d_hint_special, d->d_hint_priors, flags, 0, html ? buf_bytes : 0);
+}
+
+// run_vec_shard's kernels in its order, without its copies and waits: where
+// that function goes to the host (pool regions, chunk counts, the positions of
+// the gather) the kernels of cld_vec.hip stand.
+int cld_detect_batch_device_vec(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                                uint64_t buf_bytes, const cld_hints_dev* d_hints, const uint8_t* d_hint_text,
+                                uint64_t hint_text_bytes, uint32_t flags, int big_regions, cld_result* d_out,
+                                cld_chunk* d_chunks, uint64_t chunk_cap, uint64_t* d_chunk_offsets,
+                                int32_t* d_valid_prefix, cld_vec_status* d_status, void* stream) {
+  const bool chk = (flags & CLD_FLAG_CHECK_UTF8) != 0;
+  if ((flags & ~(CLD_FLAG_HTML | CLD_FLAG_CHECK_UTF8 | kPublicFlags)) != 0 || n > 0x7FFFFFFFu ||
+      (d_valid_prefix && !chk) || (chunk_cap > 0 && !d_chunks) || (hint_text_bytes && !d_hint_text) ||
+      (n > 0 && (!d_buf || !d_offsets || !d_out || !d_chunk_offsets || !d_status)))
+    return CLD_EINVAL;
+  int rc = cld_init(nullptr, 0);
+  if (rc) return rc;
+  if (device < 0 || device >= (int)g_devs.size()) return CLD_EINVAL;
+  std::shared_lock<std::shared_mutex> tl(g_swap_mu);
+  Device* d = g_devs[device];
+  std::lock_guard<std::mutex> lk(d->mu);
+  const bool html = (flags & CLD_FLAG_HTML) != 0, hinted = html || d_hints;
+  if (html && !d->T.ent_names) return CLD_EINVAL;   // tables without the HTML sections
+  if (hinted && !d->H.langtag1) return CLD_EINVAL;
+  HIP_OK(hipSetDevice(d->id));
+  hipStream_t s = stream ? (hipStream_t)stream : d->stream;
+  if (n == 0) {
+    if (d_chunk_offsets) HIP_OK(hipMemsetAsync(d_chunk_offsets, 0, sizeof(uint64_t), s));
+    if (d_status) HIP_OK(hipMemsetAsync(d_status, 0, sizeof(cld_vec_status), s));
+    return CLD_OK;
+  }
+  // Working memory from the bound alone: the regions of n documents of
+  // buf_bytes bytes together (the sum of len/4 rounded down is at most buf_bytes/4)
+  if (buf_bytes > (1ull << 40)) return CLD_ENOMEM;
+  const int mode = big_regions ? kVecRegionsBig : vec_pool_small() ? kVecRegionsOne : kVecRegionsSmall;
+  const uint64_t pool_chunks = mode == kVecRegionsBig   ? 8 * buf_bytes + 256 * (uint64_t)n
+                               : mode == kVecRegionsOne ? (uint64_t)n
+                                                        : buf_bytes + buf_bytes / 4 + 8 * (uint64_t)n;
+  Device::Vec& V = d->vec;
+  if (V.vslots.reserve((uint64_t)d->n_slots * cld_vec_slot_bytes()) || V.pool.reserve(pool_chunks) ||
+      V.pool_off.reserve(n + 1) || V.nch.reserve(n) || d->d_sscr.reserve(cld_strip_scratch_bytes((int)n)) ||
+      d->d_requeue.reserve(n) || d->d_requeue2.reserve(n) || d->d_lsorted.reserve(n) || d->d_lkey.reserve(n))
+    return CLD_ENOMEM;
+  if (hinted && (V.sp.reserve(n) || V.pri.reserve(16 * n))) return CLD_ENOMEM;
+  // HTML pages are rewritten into plain text with each byte's page offset
+  // (cld_html.hip); the three buffers are indexed like the text the kernels read
+  const size_t hb_bytes = std::max<size_t>(buf_bytes, 1);
+  if (html && (d->d_hbuf.reserve(hb_bytes) || d->d_hflag.reserve(hb_bytes) || d->d_hpos.reserve(2 * hb_bytes)))
+    return CLD_ENOMEM;
+  HIP_OK(hipStreamWaitEvent(s, d->done, 0));        // the previous batch may still use the scratch
+  HIP_OK(hipMemsetAsync(d_status, 0, sizeof(cld_vec_status), s));
+  HIP_OK(hipMemsetAsync(d->d_counters, 0, kCtrSlots * sizeof(uint32_t), s));
+  // CLD_FLAG_CHECK_UTF8: the kernels get the prepared batch, in which a rejected
+  // document is empty; the hints, the regions and the results go by the documents as given
+  const uint8_t* kb = d_buf;
+  const uint64_t* ko = d_offsets;
+  if (chk) {
+    if ((rc = enqueue_prepare(d, d_buf, d_offsets, n, buf_bytes, CLD_FLAG_CHECK_UTF8, s, d_valid_prefix))) return rc;
+    kb = d->p_buf;
+    ko = d->p_offs;
+  }
+  if (hinted)
+    HIP_OK(cld_launch_apply_hints(&d->H, d_buf, d_offsets, (int)n, d_hints, d_hint_text, hint_text_bytes, !html,
+                                  nullptr, V.pri, V.sp, s));
+  uint64_t* scan = (uint64_t*)(uint8_t*)d->d_sscr;
+  HIP_OK(cld_launch_vec_plan(d_offsets, (int)n, mode, scan, s));
+  HIP_OK(cld_launch_scan_lengths((int)n, V.pool_off, scan, s));
+  uint8_t *hb = nullptr, *hf = nullptr;
+  uint32_t *hpz = nullptr, *hgz = nullptr;
+  if (html) {
+    hb = d->d_hbuf;
+    hf = d->d_hflag;
+    hpz = d->d_hpos;
+    hgz = d->d_hpos + hb_bytes;
+    HIP_OK(cld_launch_html_rewrite(d->d_T, kb, ko, (int)n, V.sp, hb, hf, hpz, hgz, 0, nullptr, s));
+  }
+  HIP_OK(cld_launch_route_vec((int)n, d->d_counters, d->d_requeue, s));
+  HIP_OK(cld_launch_order_long(ko, d->d_requeue, d->d_counters, d->d_lkey, d->d_lhist, d->d_lsorted, false, s));
+  HIP_OK(cld_launch_long_vec(d->d_T, kb, ko, d->d_lsorted, d_out, d->d_slots, V.vslots, d->n_slots, d->d_requeue2,
+                             d->d_counters, flags & kCldFlags, hinted ? (const uint8_t*)V.sp : nullptr,
+                             hinted ? (const uint32_t*)V.pri : nullptr, hb, hf, hpz, hgz, V.pool, V.pool_off, V.nch,
+                             s));
+  if (chk && (rc = enqueue_fixup(d, d_out, n, s, V.nch))) return rc;
+  HIP_OK(cld_launch_vec_finish(d_offsets, (int)n, V.nch, chk ? d->chk_vp : nullptr, d_out,
+                               g_tab.meta.unknown_language, scan, d_status, s));
+  HIP_OK(cld_launch_scan_lengths((int)n, d_chunk_offsets, scan, s));
+  HIP_OK(cld_launch_vec_gather_chunks(V.pool, V.pool_off, d_chunk_offsets, (int)n, d_chunks, chunk_cap, d_status, s));
+  HIP_OK(hipEventRecord(d->done, s));
+  return CLD_OK;
 }
 
 int cld_prepare_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, uint32_t flags,
