@@ -381,6 +381,77 @@ int cld_detect_batch_device_vec(int device, const uint8_t* d_buf, const uint64_t
                                 uint64_t chunk_cap, uint64_t* d_chunk_offsets,
                                 int32_t* d_valid_prefix, cld_vec_status* d_status, void* stream);
 
+/* ---- Per-document is_plain_text and CLD2 flags within one batch.
+ * ExtDetectLanguageSummary takes is_plain_text and flags per call
+ * (compact_lang_det.h:324-335); the entries above take one value of each for
+ * the whole batch.  The four _docflags entries take one more array,
+ * doc_flags[n], one word per document, so that a batch of n documents stays n
+ * independent calls of the reference -- a crawl shard of text/html and
+ * text/plain records, some of them wanting best-effort answers, is one batch.
+ * Document i is scored as the reference scores it with
+ *   is_plain_text = !((flags | doc_flags[i]) & CLD_FLAG_HTML)
+ *   flags         = (flags | doc_flags[i]) & (CLD_FLAG_SCORE_AS_QUADS | CLD_FLAG_BEST_EFFORT)
+ * (kCLDFlagScoreAsQuads, scoreonescriptspan.cc:1318-1320; kCLDFlagBestEffort,
+ * compact_lang_det_impl.cc:1998-2000, :1493; the lang= scan of the first 8 KB,
+ * impl.cc:1596-1611, runs for the documents that are HTML and only for them).
+ * A bit set in `flags` holds for every document; a word can add bits, never
+ * take one away.  The debug-output bits (CLD_FLAG_DEBUG_MASK) are accepted
+ * and ignored in the words as in `flags`.  `flags` keeps the meaning it has
+ * in the entry each one extends, CLD_FLAG_CHECK_UTF8 included; hints stay per
+ * document.  The preparation flags and the UTF-8 check are per batch only.
+ * doc_flags == NULL: exactly the entry it extends (the call is forwarded).
+ *
+ * Host entries: a word with any bit outside CLD_FLAG_HTML |
+ * CLD_FLAG_SCORE_AS_QUADS | CLD_FLAG_BEST_EFFORT | CLD_FLAG_DEBUG_MASK
+ * (CLD_FLAG_STRIP_EXTRAS, CLD_FLAG_CSTRING, CLD_FLAG_CHECK_UTF8, unknown bits)
+ * gives CLD_EINVAL, before any GPU work.  Words that are all zero cost
+ * nothing: the call is then cld_detect_batch_ex's.  Otherwise the batch
+ * carries one routing byte per document to the GPU (as a hinted batch does),
+ * and when some document is HTML the HTML working memory of
+ * cld_detect_batch_ex: per chunk two bytes per text byte, ten where a chunk
+ * holds 40928 bytes or more.
+ *
+ *   cld_detect_batch_docflags      cld_detect_batch_ex; with CLD_FLAG_CHECK_UTF8
+ *                                  in flags also cld_detect_batch_checked:
+ *                                  valid_prefix (NULL: not wanted; n entries)
+ *                                  receives SpanInterchangeValid per document.
+ *                                  valid_prefix without the flag: CLD_EINVAL.
+ *   cld_detect_batch_vec_docflags  cld_detect_batch_vec, with its errors
+ *                                  (chunk_offsets NULL, chunk_cap > 0 without
+ *                                  chunks: CLD_EINVAL; CLD_ENOSPC; CLD_EIO). */
+int cld_detect_batch_docflags(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
+                              const uint32_t* doc_flags, uint32_t flags, cld_result* out, int32_t* valid_prefix);
+int cld_detect_batch_vec_docflags(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
+                                  const uint32_t* doc_flags, uint32_t flags, cld_result* out, cld_chunk* chunks,
+                                  size_t chunk_cap, uint64_t* chunk_offsets);
+
+/* The same for device-resident input: cld_detect_batch_device_hints and
+ * cld_detect_batch_device_vec with d_doc_flags[n] in device memory of GPU
+ * `device`; every other argument, the asynchrony and the errors are theirs
+ * (flags: CLD_FLAG_HTML and the public CLD2 flags; the vector entry also
+ * CLD_FLAG_CHECK_UTF8).  d_doc_flags == NULL forwards to them.
+ * The host never reads the words, so it cannot reject one: the ApplyHints
+ * kernel (cld_hints.hip) masks each word to CLD_FLAG_HTML |
+ * CLD_FLAG_SCORE_AS_QUADS | CLD_FLAG_BEST_EFFORT and ignores every other bit,
+ * stray high bits included.  For the same reason the host cannot know whether
+ * any document is HTML, so with d_doc_flags the call is set up as an HTML
+ * batch is: the tables must hold the HTML and hint sections (CLD_EINVAL
+ * otherwise), ApplyHints always runs, the 16 langprobs per document always go
+ * along (64 n bytes, plus n routing bytes), and the HTML working memory is
+ * sized from buf_bytes -- 2 buf_bytes, and 8 buf_bytes more in the vector
+ * entry or where buf_bytes >= 40928 (each rewritten byte's page offset).
+ * CLD_ENOMEM, synchronously, if that does not fit. */
+int cld_detect_batch_device_docflags(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                                     uint64_t buf_bytes, const cld_hints_dev* d_hints, const uint8_t* d_hint_text,
+                                     uint64_t hint_text_bytes, const uint32_t* d_doc_flags, cld_result* d_out,
+                                     uint32_t flags, void* stream);
+int cld_detect_batch_device_vec_docflags(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                                         uint64_t buf_bytes, const cld_hints_dev* d_hints, const uint8_t* d_hint_text,
+                                         uint64_t hint_text_bytes, const uint32_t* d_doc_flags, uint32_t flags,
+                                         int big_regions, cld_result* d_out, cld_chunk* d_chunks, uint64_t chunk_cap,
+                                         uint64_t* d_chunk_offsets, int32_t* d_valid_prefix, cld_vec_status* d_status,
+                                         void* stream);
+
 /* The preparation step alone, on GPU 0 (host buffers): out_buf receives the
  * prepared documents back to back (capacity >= offsets[n]-offsets[0] + n
  * bytes), out_offsets[0..n] their offsets.  flags: CLD_FLAG_STRIP_EXTRAS and/or

@@ -51,7 +51,9 @@ EXPORTS = ("detect_language", "cld_init", "cld_init_device", "cld_shutdown", "cl
            "cld_kernel_times", "cld_detect_batch_ex", "cld_hint_priors", "cld_detect_batch_vec",
            "cld_detect_batch_checked", "cld_valid_prefix_host", "cld_valid_prefix_batch",
            "cld_valid_prefix_device", "detect_language_checked", "cld_hint_boosts_device",
-           "cld_detect_batch_device_hints", "cld_detect_batch_device_vec")
+           "cld_detect_batch_device_hints", "cld_detect_batch_device_vec", "cld_detect_batch_docflags",
+           "cld_detect_batch_vec_docflags", "cld_detect_batch_device_docflags",
+           "cld_detect_batch_device_vec_docflags")
 CHUNK_DTYPE = np.dtype([("offset", "<i4"), ("bytes", "<i4"), ("lang1", "<u2"), ("pad", "<u2")])   # cld_chunk
 
 
@@ -189,6 +191,12 @@ def lib():
                                                   ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_void_p]
+        vp, sz, u32, u64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint64
+        L.cld_detect_batch_docflags.argtypes = [vp, vp, sz, vp, vp, u32, vp, vp]
+        L.cld_detect_batch_vec_docflags.argtypes = [vp, vp, sz, vp, vp, u32, vp, vp, sz, vp]
+        L.cld_detect_batch_device_docflags.argtypes = [ctypes.c_int, vp, vp, sz, u64, vp, vp, u64, vp, vp, u32, vp]
+        L.cld_detect_batch_device_vec_docflags.argtypes = [ctypes.c_int, vp, vp, sz, u64, vp, vp, u64, vp, u32,
+                                                           ctypes.c_int, vp, vp, u64, vp, vp, vp, vp]
         L.detect_language_checked.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
         L.detect_language_checked.restype = ctypes.c_char_p
         _lib = L
@@ -442,6 +450,110 @@ def detect_batch_device_vec(device, d_buf_ptr, d_offsets_ptr, n, buf_bytes, d_ou
                                            d_valid_prefix_ptr, d_status_ptr, stream_ptr)
     if rc != 0:
         raise CldError("cld_detect_batch_device_vec failed: %d" % rc)
+
+
+def _doc_flags(doc_flags, n):
+    """doc_flags of the _docflags entries: None, or one uint32 word per document."""
+    if doc_flags is None:
+        return None
+    a = np.ascontiguousarray(doc_flags, dtype=np.uint32)
+    if a.shape != (n,):
+        raise ValueError("need one doc_flags word per document")
+    return a
+
+
+def detect_batch_docflags(docs=None, buf=None, offsets=None, hints=None, doc_flags=None, flags=0, valid_prefix=False):
+    """cld_detect_batch_docflags: detect_batch_ex with is_plain_text and CLD2's flags per
+    document -- document i is scored with flags | doc_flags[i] (FLAG_HTML, FLAG_SCORE_AS_QUADS,
+    FLAG_BEST_EFFORT; doc_flags: uint32[n] or None).  flags as for detect_batch_ex; with
+    FLAG_CHECK_UTF8 and valid_prefix=True -> (results, valid_prefix int32[n])."""
+    if docs is not None:
+        buf, offsets = pack(docs)
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    out = np.zeros(n, dtype=RESULT_DTYPE)
+    vp = np.zeros(n, dtype=np.int32) if valid_prefix else None
+    df = _doc_flags(doc_flags, n)
+    harr = None
+    if hints is not None:
+        if len(hints) != n:
+            raise ValueError("need one Hints per document")
+        harr = (Hints * n)(*hints) if n else None
+    bptr = buf.ctypes.data if buf.size else ctypes.addressof(ctypes.c_uint8(0))
+    rc = lib().cld_detect_batch_docflags(bptr, offsets.ctypes.data, n,
+                                         ctypes.cast(harr, ctypes.c_void_p) if harr else None,
+                                         df.ctypes.data if df is not None and n else None, flags, out.ctypes.data,
+                                         vp.ctypes.data if vp is not None else None)
+    value = (out, vp) if valid_prefix else out
+    if rc == EIO:
+        raise PartialBatchError("cld_detect_batch_docflags", value, out["summary_lang"] == LANG_FAILED)
+    if rc != 0:
+        raise CldError("cld_detect_batch_docflags failed: %d" % rc)
+    return value
+
+
+def detect_batch_vec_docflags(docs=None, buf=None, offsets=None, hints=None, doc_flags=None, chunk_cap=None, flags=0):
+    """cld_detect_batch_vec_docflags: detect_batch_vec with is_plain_text and CLD2's flags per
+    document (doc_flags: uint32[n] or None, as for detect_batch_docflags)."""
+    if docs is not None:
+        buf, offsets = pack(docs)
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    out = np.zeros(n, dtype=RESULT_DTYPE)
+    coffs = np.zeros(n + 1, dtype=np.uint64)
+    if n == 0:
+        return out, np.zeros(0, dtype=CHUNK_DTYPE), coffs
+    df = _doc_flags(doc_flags, n)
+    harr = None
+    if hints is not None:
+        if len(hints) != n:
+            raise ValueError("need one Hints per document")
+        harr = (Hints * n)(*hints)
+    cap = chunk_cap if chunk_cap is not None else 4 * n + 1024
+    bptr = buf.ctypes.data if buf.size else ctypes.addressof(ctypes.c_uint8(0))
+    for _ in range(2):                                     # second try with the exact size
+        chunks = np.zeros(max(cap, 1), dtype=CHUNK_DTYPE)
+        rc = lib().cld_detect_batch_vec_docflags(bptr, offsets.ctypes.data, n,
+                                                 ctypes.cast(harr, ctypes.c_void_p) if harr else None,
+                                                 df.ctypes.data if df is not None else None, flags, out.ctypes.data,
+                                                 chunks.ctypes.data, cap, coffs.ctypes.data)
+        if rc == 0:
+            return out, chunks[:int(coffs[-1])], coffs
+        if rc == EIO:                                      # some document got no vector (an empty one)
+            raise PartialBatchError("cld_detect_batch_vec_docflags", (out, chunks[:int(coffs[-1])], coffs),
+                                    out["summary_lang"] == LANG_FAILED)
+        if rc != ENOSPC or chunk_cap is not None:
+            break
+        cap = int(coffs[-1])
+    raise CldError("cld_detect_batch_vec_docflags failed: %d" % rc)
+
+
+def detect_batch_device_docflags(device, d_buf_ptr, d_offsets_ptr, n, buf_bytes, d_out_ptr, d_doc_flags_ptr=None,
+                                 d_hints_ptr=None, d_hint_text_ptr=None, hint_text_bytes=0, flags=0, stream_ptr=None):
+    """cld_detect_batch_device_docflags: detect_batch_device_hints with d_doc_flags_ptr, uint32[n]
+    in device memory (None: exactly that call); the kernel masks each word to FLAG_HTML |
+    FLAG_SCORE_AS_QUADS | FLAG_BEST_EFFORT."""
+    rc = lib().cld_detect_batch_device_docflags(device, d_buf_ptr, d_offsets_ptr, n, buf_bytes, d_hints_ptr,
+                                                d_hint_text_ptr, hint_text_bytes, d_doc_flags_ptr, d_out_ptr, flags,
+                                                stream_ptr)
+    if rc != 0:
+        raise CldError("cld_detect_batch_device_docflags failed: %d" % rc)
+
+
+def detect_batch_device_vec_docflags(device, d_buf_ptr, d_offsets_ptr, n, buf_bytes, d_out_ptr, d_chunks_ptr,
+                                     chunk_cap, d_chunk_offsets_ptr, d_status_ptr, d_doc_flags_ptr=None,
+                                     d_hints_ptr=None, d_hint_text_ptr=None, hint_text_bytes=0, flags=0,
+                                     big_regions=False, d_valid_prefix_ptr=None, stream_ptr=None):
+    """cld_detect_batch_device_vec_docflags: detect_batch_device_vec with d_doc_flags_ptr,
+    uint32[n] in device memory (None: exactly that call)."""
+    rc = lib().cld_detect_batch_device_vec_docflags(device, d_buf_ptr, d_offsets_ptr, n, buf_bytes, d_hints_ptr,
+                                                    d_hint_text_ptr, hint_text_bytes, d_doc_flags_ptr, flags,
+                                                    1 if big_regions else 0, d_out_ptr, d_chunks_ptr, chunk_cap,
+                                                    d_chunk_offsets_ptr, d_valid_prefix_ptr, d_status_ptr, stream_ptr)
+    if rc != 0:
+        raise CldError("cld_detect_batch_device_vec_docflags failed: %d" % rc)
 
 
 def last_stats(device=0):

@@ -453,12 +453,17 @@ __global__ __launch_bounds__(64) void k_apply_hints(DevHints H, const uint8_t* _
                                                      const uint64_t* __restrict__ offs, int n,
                                                      const cld_hints_dev* __restrict__ hints,
                                                      const uint8_t* __restrict__ hint_text, uint64_t hint_text_bytes,
-                                                     int plain, int16_t* __restrict__ priors14,
+                                                     int plain, const uint32_t* __restrict__ doc_flags,
+                                                     int16_t* __restrict__ priors14,
                                                      uint32_t* __restrict__ boosts16, uint8_t* __restrict__ special) {
   __shared__ __align__(16) Smem sm;
   Smem* s = &sm;
   const int doc = blockIdx.x, lane = threadIdx.x;
   if (doc >= n) return;
+  // the document's own mode (the _docflags entries): the word is the caller's,
+  // possibly unchecked device memory, so only its three bits count
+  const uint32_t df = doc_flags ? doc_flags[doc] & (CLD_FLAG_HTML | CLD_FLAG_SCORE_AS_QUADS | CLD_FLAG_BEST_EFFORT) : 0u;
+  if (df & CLD_FLAG_HTML) plain = 0;
   ((uint32_t*)s->action)[lane] = ((const uint32_t*)H.action)[lane];
   ((uint32_t*)s->remap)[lane] = ((const uint32_t*)H.remap)[lane];
   int np = 0;                                          // priors so far (lane 0's counts)
@@ -560,7 +565,8 @@ __global__ __launch_bounds__(64) void k_apply_hints(DevHints H, const uint8_t* _
         any |= s->ring[k];
         if (boosts16) boosts16[(size_t)doc * 16 + k] = s->ring[k];
       }
-      if (special) special[doc] = (uint8_t)((plain ? 0 : kSpecialHtml) | (any ? kSpecialPriors : 0));
+      if (special)
+        special[doc] = (uint8_t)((plain ? 0 : kSpecialHtml) | (any ? kSpecialPriors : 0) | cld_cflags_special(df));
     }
   }
 }
@@ -569,10 +575,10 @@ __global__ __launch_bounds__(64) void k_apply_hints(DevHints H, const uint8_t* _
 
 extern "C" hipError_t cld_launch_apply_hints(const DevHints* H, const uint8_t* buf, const uint64_t* offs, int n,
                                              const cld_hints_dev* hints, const uint8_t* hint_text,
-                                             uint64_t hint_text_bytes, int plain, int16_t* priors14,
-                                             uint32_t* boosts16, uint8_t* special, hipStream_t s) {
+                                             uint64_t hint_text_bytes, int plain, const uint32_t* doc_flags,
+                                             int16_t* priors14, uint32_t* boosts16, uint8_t* special, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(hnt::k_apply_hints, dim3(n), dim3(64), 0, s, *H, buf, offs, n, hints, hint_text, hint_text_bytes,
-                     plain, priors14, boosts16, special);
+                     plain, doc_flags, priors14, boosts16, special);
   return hipGetLastError();
 }

@@ -40,7 +40,23 @@ enum { kCtrRequeue = 0, kCtrDequeue = 1, kCtrPass1 = 2, kCtrPass2 = 3, kCtrPass3
 // span source.  kSpecialNoVec (vec mode): a rewritten page whose offset map the
 // parallel span builder cannot reproduce (cld_html.hip); k_long<VEC> scans the
 // original page with the sequential span source.
-enum : uint8_t { kSpecialHtml = 1, kSpecialPriors = 2, kSpecialRewritten = 4, kSpecialNoVec = 8 };
+// kSpecialQuads / kSpecialBestEffort (the _docflags entries): the document's
+// own kCLDFlagScoreAsQuads / kCLDFlagBestEffort, on top of the batch's cflags.
+enum : uint8_t { kSpecialHtml = 1, kSpecialPriors = 2, kSpecialRewritten = 4, kSpecialNoVec = 8,
+                 kSpecialQuads = 16, kSpecialBestEffort = 32 };
+// The CLD2 flags a routing byte carries (0 for a byte without the two bits,
+// so a batch without per-document flags scores with cflags alone), and back.
+constexpr uint32_t cld_special_cflags(uint32_t sp) {
+  return ((sp & kSpecialQuads) << 4) | ((sp & kSpecialBestEffort) << 9);
+}
+constexpr uint8_t cld_cflags_special(uint32_t flags) {
+  return (uint8_t)(((flags & CLD_FLAG_SCORE_AS_QUADS) >> 4) | ((flags & CLD_FLAG_BEST_EFFORT) >> 9));
+}
+static_assert(cld_special_cflags(kSpecialQuads) == CLD_FLAG_SCORE_AS_QUADS &&
+                  cld_special_cflags(kSpecialBestEffort) == CLD_FLAG_BEST_EFFORT &&
+                  cld_cflags_special(CLD_FLAG_SCORE_AS_QUADS | CLD_FLAG_BEST_EFFORT) ==
+                      (kSpecialQuads | kSpecialBestEffort),
+              "routing bits <-> CLD2 flags");
 // k_long: waves per workgroup
 constexpr int kLongWPB = 4;
 
@@ -86,7 +102,9 @@ hipError_t cld_launch_vec_gather_chunks(const cld_chunk* pool, const uint64_t* p
 // ones (kSpecialPriors) are scored with their 16 ApplyHints langprobs
 // (priors + 16 * i; k_long reads the same two arrays).
 // cflags (every launcher): the caller's public CLD2 flags, CLD_FLAG_SCORE_AS_QUADS /
-// CLD_FLAG_BEST_EFFORT (compact_lang_det.h:343, :349), the same for every document.
+// CLD_FLAG_BEST_EFFORT (compact_lang_det.h:343, :349), the same for every document;
+// a document whose routing byte carries kSpecialQuads / kSpecialBestEffort is
+// scored with cflags | cld_special_cflags(special[i]).
 hipError_t cld_launch_wave(const DevTables* T, const uint8_t* buf, const uint64_t* offs, int n,
                            cld_result* out, uint32_t* requeue_list, uint32_t* counters,
                            unsigned long long* prof, const uint8_t* special, uint32_t* special_list,
@@ -165,10 +183,15 @@ hipError_t cld_launch_valid_fixup(const uint64_t* offs, int n, const int32_t* va
 // routing byte: kSpecialHtml unless plain, kSpecialPriors when a langprob is
 // non-zero); each nullable.  hints (nullable): one record per document, its
 // content-language text in hint_text[0, hint_text_bytes).  plain 0: the lang=
-// scan of each document's first 8 KB.  H by value to the kernel.
+// scan of each document's first 8 KB.  doc_flags (nullable): one word per
+// document, masked to CLD_FLAG_HTML | SCORE_AS_QUADS | BEST_EFFORT: document i
+// is HTML (scan, kSpecialHtml) when plain is 0 or its word says so, and its
+// two CLD2 flags go into special as kSpecialQuads / kSpecialBestEffort.
+// H by value to the kernel.
 hipError_t cld_launch_apply_hints(const DevHints* H, const uint8_t* buf, const uint64_t* offs, int n,
                                   const cld_hints_dev* hints, const uint8_t* hint_text, uint64_t hint_text_bytes,
-                                  int plain, int16_t* priors14, uint32_t* boosts16, uint8_t* special, hipStream_t s);
+                                  int plain, const uint32_t* doc_flags, int16_t* priors14, uint32_t* boosts16,
+                                  uint8_t* special, hipStream_t s);
 // fault_doc (k_long): test hook, batch index of a document made to fail
 // (0xFFFFFFFF: none): it gets no result (summary CLD_LANG_FAILED).
 // seq_list (n entries, counters[kCtrRequeue2]): the documents k_long hands to

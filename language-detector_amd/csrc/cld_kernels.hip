@@ -85,8 +85,11 @@ __global__ __launch_bounds__(64 * WPB, WAVE_WPS) void k_wave(DevTables T, const 
   // the accounting atomics do not themselves become the bottleneck
   // a rewritten HTML page (cld_html.hip) is read from hbuf, with its lookahead marks
   const bool rw = (sp & kSpecialRewritten) != 0;
+  // the document's own ScoreAsQuads / BestEffort ride in its routing byte (i is
+  // wave-uniform, so this stays scalar)
+  const uint32_t dcf = cflags | cld_special_cflags(sp);
   const bool rq = !wave::detect<CAP>(T, (rw ? hbuf : buf) + a, (int)len, smem[wv], lane, &out[i],
-                                     (i & 63) == 0 ? prof : nullptr, cflags, pri, rw ? hflag + a : nullptr);
+                                     (i & 63) == 0 ? prof : nullptr, dcf, pri, rw ? hflag + a : nullptr);
   if (rq && lane == 0) {                       // rare (state-machine or capacity cases)
     if (requeue_list) {
       uint32_t k = atomicAdd(&counters[kCtrRequeue], 1u);
@@ -230,6 +233,7 @@ __global__ __launch_bounds__(64 * WPB, LNG_WPS) void k_long(const DevTables* __r
     const uint32_t* hp = hbig ? hpos + a : nullptr;
     const uint32_t* hg = hbig ? hgap + a : nullptr;
     const uint32_t* pri = (spi & kSpecialPriors) ? priors + 16ull * i : nullptr;
+    const uint32_t dcf = cflags | cld_special_cflags(spi);   // with the document's own CLD2 flags
     // The sequential span source (cld_seq.hip) over the page as given: for a
     // page the HTML rewrite did not take (still kSpecialHtml), one whose
     // rewritten offsets vec mode cannot use (kSpecialNoVec), a document past
@@ -263,11 +267,11 @@ __global__ __launch_bounds__(64 * WPB, LNG_WPS) void k_long(const DevTables* __r
     if (!fault && !to_seq) {
       if constexpr (SEQ) {
         const lng::SeqDoc sq{buf + a, (int)len, !(spi & (kSpecialHtml | kSpecialRewritten | kSpecialNoVec))};
-        passes = lng::detect<DIAG, VEC, true>(T, buf + a, (int)len, S, smem[wv], lane, o, tr, i, cflags, pri, nullptr,
+        passes = lng::detect<DIAG, VEC, true>(T, buf + a, (int)len, S, smem[wv], lane, o, tr, i, dcf, pri, nullptr,
                                               VEC ? &V : nullptr, lng::kPassesAll, nullptr, nullptr, &sq);
         if (lane == 0) atomicAdd(&counters[kCtrSeq], 1u);
       } else {
-        passes = lng::detect<DIAG, VEC>(T, (rw ? hbuf : buf) + a, (int)len, S, smem[wv], lane, o, tr, i, cflags,
+        passes = lng::detect<DIAG, VEC>(T, (rw ? hbuf : buf) + a, (int)len, S, smem[wv], lane, o, tr, i, dcf,
                                         pri, rw ? hflag + a : nullptr, VEC ? &V : nullptr, VEC ? lng::kPassesAll : mode,
                                         hp, hg);
       }
@@ -502,7 +506,7 @@ __global__ __launch_bounds__(64 * kStWPB, LNG_ST_WPS) void k_lscore(
     if (P2 && at == lng::kStNone) continue;      // k_lrep handed it to the fused k_long
     const uint32_t i = list[k];
     const uint8_t spi = special ? special[i] : (uint8_t)0;
-    const int r = lng::st_score(T, S, smem[wv], pool + at, P2, &out[i], cflags,
+    const int r = lng::st_score(T, S, smem[wv], pool + at, P2, &out[i], cflags | cld_special_cflags(spi),
                                 (spi & kSpecialPriors) ? priors + 16ull * i : nullptr, lane);
     const uint32_t nsp = (!P2 && r == 0) ? wave::uflu(gld(&reinterpret_cast<const lng::StHdr*>(pool + at)->nsp)) : 0u;
     if (lane == 0) {
@@ -554,7 +558,7 @@ __global__ __launch_bounds__(64 * kStWPB, LNG_ST_WPS) void k_lgroup(
     const uint8_t spi = special ? special[i] : (uint8_t)0;
     const int nsp = (int)wave::uflu(gld(&reinterpret_cast<const lng::StHdr*>(pool + at)->nsp));
     const int j0 = (int)g * lng::kParG, j1 = min(nsp, j0 + lng::kParG);
-    (void)lng::st_group(T, S, smem[wv], pool + at, j0, j1, cflags,
+    (void)lng::st_group(T, S, smem[wv], pool + at, j0, j1, cflags | cld_special_cflags(spi),
                         (spi & kSpecialPriors) ? priors + 16ull * i : nullptr, lane);
   }
 }
@@ -564,7 +568,8 @@ __global__ __launch_bounds__(64 * kStWPB, LNG_ST_WPS) void k_lfinish(
     const DevTables* __restrict__ Tp, const uint32_t* __restrict__ list, cld_result* __restrict__ out,
     uint8_t* __restrict__ pool, const uint64_t* __restrict__ meta, uint32_t* __restrict__ par_lists, uint32_t n,
     uint64_t* __restrict__ group_list2, uint32_t gcap, uint32_t* __restrict__ p2_list,
-    uint32_t* __restrict__ fall_list, uint32_t* __restrict__ counters, uint32_t cflags) {
+    uint32_t* __restrict__ fall_list, uint32_t* __restrict__ counters, uint32_t cflags,
+    const uint8_t* __restrict__ special) {
   __shared__ FinSmem smem[kStWPB];
   const DevTables& T = *Tp;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -579,7 +584,8 @@ __global__ __launch_bounds__(64 * kStWPB, LNG_ST_WPS) void k_lfinish(
     const uint64_t at = meta[k];
     if (P2 && at == lng::kStNone) continue;      // k_lrep handed it to the fused k_long
     const uint32_t i = list[k];
-    const int r = lng::st_par_finish(T, smem[wv], pool + at, P2, &out[i], cflags, lane);
+    const uint8_t spi = special ? special[i] : (uint8_t)0;   // (the document's own BestEffort)
+    const int r = lng::st_par_finish(T, smem[wv], pool + at, P2, &out[i], cflags | cld_special_cflags(spi), lane);
     if (r == 0 && !P2) {                         // pass 2: Repeats (k_lrep), then its groups again
       const int nsp = (int)wave::uflu(gld(&reinterpret_cast<const lng::StHdr*>(pool + at)->nsp));
       const uint32_t ng = (uint32_t)(nsp + lng::kParG - 1) / lng::kParG;
@@ -857,7 +863,7 @@ hipError_t cld_launch_staged(const DevTables* d_T, const uint8_t* buf, const uin
   hipLaunchKernelGGL(cld::k_lgroup<false>, gst, bst, 0, s, d_T, list, slots, pool, meta, gl1, gc, counters, cflags,
                      special, priors);
   hipLaunchKernelGGL(cld::k_lfinish<false>, gst, bst, 0, s, d_T, list, out, pool, meta, par_lists, nn, gl2, gc,
-                     p2_list, fall_list, counters, cflags);
+                     p2_list, fall_list, counters, cflags, special);
   hipLaunchKernelGGL(cld::k_lrep, dim3(cus * 4 * LNG_REP_WPS), dim3(64), 0, s, list, slots, pool, meta, p2_list,
                      fall_list, counters, nn);
   hipLaunchKernelGGL(cld::k_lscore<true>, gst, bst, 0, s, d_T, list, out, slots, pool, meta, p2_list, p2_list,
@@ -865,7 +871,7 @@ hipError_t cld_launch_staged(const DevTables* d_T, const uint8_t* buf, const uin
   hipLaunchKernelGGL(cld::k_lgroup<true>, gst, bst, 0, s, d_T, list, slots, pool, meta, gl2, gc, counters, cflags,
                      special, priors);
   hipLaunchKernelGGL(cld::k_lfinish<true>, gst, bst, 0, s, d_T, list, out, pool, meta, par_lists, nn, gl2, gc,
-                     p2_list, fall_list, counters, cflags);
+                     p2_list, fall_list, counters, cflags, special);
   return hipGetLastError();
 }
 

@@ -1193,7 +1193,7 @@ struct Batch {
   uint32_t flags = 0;
   const uint8_t* special = nullptr;    // cld_detect_batch_ex (nullable): routing bits, one per document,
   const uint32_t* priors = nullptr;    //   and ApplyHints langprobs, 16 per document
-  bool html = false;
+  bool html = false;                   // some document is HTML (special & kSpecialHtml)
   int32_t* vp_out = nullptr;           // cld_detect_batch_checked (nullable): the valid prefixes go here
 
   DocRef doc(size_t i) const { return DocRef{buf + offs[i], (size_t)(offs[i + 1] - offs[i])}; }
@@ -2314,14 +2314,29 @@ namespace {
 // ApplyHints per document on the host (a few table lookups, and for HTML a
 // scan of the first 8 KB), split over host threads: the routing bits and,
 // when any document has a prior, the 16 langprobs per document.  The caller
-// holds g_swap_mu (shared).
+// holds g_swap_mu (shared).  html: every document is HTML; doc_flags (the
+// _docflags entries, nullable, validated by the caller): document i is HTML
+// when its word carries CLD_FLAG_HTML too, and its own ScoreAsQuads /
+// BestEffort go into its routing byte (kSpecialQuads / kSpecialBestEffort).
+// *any_html: some document is HTML; *routed: some routing byte is not zero.
 int apply_hints(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints, bool html,
-                std::vector<uint8_t>* special, std::vector<uint32_t>* priors) {
-  if (html && !g_tab.offs.ent_names) return CLD_EINVAL;     // tables without the HTML sections
-  if ((html || hints) && !g_tab.hints.ok()) return CLD_EINVAL;
+                const uint32_t* doc_flags, std::vector<uint8_t>* special, std::vector<uint32_t>* priors,
+                bool* any_html, bool* routed) {
   special->assign(n, html ? kSpecialHtml : 0);
+  bool some_html = html, some_bits = html;
+  if (doc_flags)
+    for (size_t i = 0; i < n; ++i) {
+      const uint8_t sp = (uint8_t)(((doc_flags[i] & CLD_FLAG_HTML) ? kSpecialHtml : 0) | cld_cflags_special(doc_flags[i]));
+      (*special)[i] |= sp;
+      some_html |= ((*special)[i] & kSpecialHtml) != 0;
+      some_bits |= (*special)[i] != 0;
+    }
+  *any_html = some_html;
+  *routed = some_bits;
   priors->clear();
-  if (!(html || hints)) return CLD_OK;
+  if (*any_html && !g_tab.offs.ent_names) return CLD_EINVAL;     // tables without the HTML sections
+  if ((*any_html || hints) && !g_tab.hints.ok()) return CLD_EINVAL;
+  if (!(*any_html || hints)) return CLD_OK;
   priors->assign(16 * n, 0);
   std::atomic<bool> any(false);
   const int nt = (int)std::max<size_t>(1, std::min<size_t>(std::max(1u, std::thread::hardware_concurrency()),
@@ -2330,7 +2345,8 @@ int apply_hints(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld
     bool a = false;
     for (size_t i = lo; i < hi; ++i) {
       int16_t p[cld::kMaxPriors];
-      const int k = cld::hint_priors(g_tab.hints, buf + offsets[i], offsets[i + 1] - offsets[i], !html,
+      const bool page = ((*special)[i] & kSpecialHtml) != 0;   // (the lang= scan of this document's first 8 KB)
+      const int k = cld::hint_priors(g_tab.hints, buf + offsets[i], offsets[i + 1] - offsets[i], !page,
                                      hints ? hints + i : nullptr, p);
       if (k <= 0) continue;
       uint32_t* o = priors->data() + 16 * i;
@@ -2351,12 +2367,26 @@ int apply_hints(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld
 
 }  // namespace
 
+// A per-document mode word of the host _docflags entries: CLD_FLAG_HTML and the
+// reference's public flags only (no preparation flag, no CLD_FLAG_CHECK_UTF8).
+static bool doc_flags_ok(const uint32_t* doc_flags, size_t n) {
+  uint32_t all = 0;
+  for (size_t i = 0; i < n; ++i) all |= doc_flags[i];
+  return (all & ~(CLD_FLAG_HTML | kPublicFlags)) == 0;
+}
+
+static int detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
+                            const uint32_t* doc_flags, uint32_t flags, cld_result* out, cld_chunk* chunks,
+                            size_t chunk_cap, uint64_t* chunk_offsets);
+
 // cld_detect_batch_ex, and with vp (n entries) cld_detect_batch_checked: the
 // valid prefixes of a CLD_FLAG_CHECK_UTF8 batch come back with the results.
+// doc_flags (nullable): cld_detect_batch_docflags' per-document words.
 static int detect_batch_ex(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
-                           uint32_t flags, cld_result* out, int32_t* vp) {
+                           uint32_t flags, cld_result* out, int32_t* vp, const uint32_t* doc_flags = nullptr) {
   if ((flags & ~(CLD_FLAG_HTML | CLD_FLAG_CHECK_UTF8 | kPublicFlags)) != 0) return CLD_EINVAL;
   if (int rc = check_batch(buf, offsets, n, out)) return rc;
+  if (doc_flags && !doc_flags_ok(doc_flags, n)) return CLD_EINVAL;
   if (n == 0) return CLD_OK;
   if ((flags & CLD_FLAG_CHECK_UTF8) && !docs_fit_int32(offsets, n)) return CLD_EINVAL;
   int rc = cld_init(nullptr, 0);
@@ -2365,9 +2395,11 @@ static int detect_batch_ex(const uint8_t* buf, const uint64_t* offsets, size_t n
   const uint32_t cf = flags & (kCldFlags | CLD_FLAG_CHECK_UTF8);
   std::vector<uint8_t> special;
   std::vector<uint32_t> priors;
-  const bool html = (flags & CLD_FLAG_HTML) != 0;
-  if ((rc = apply_hints(buf, offsets, n, hints, html, &special, &priors))) return rc;
-  const Batch b{buf, offsets, n, out, cf, (html || !priors.empty()) ? special.data() : nullptr,
+  bool html = false, routed = false;           // some document is HTML; some routing byte is set
+  if ((rc = apply_hints(buf, offsets, n, hints, (flags & CLD_FLAG_HTML) != 0, doc_flags, &special, &priors, &html,
+                        &routed)))
+    return rc;
+  const Batch b{buf, offsets, n, out, cf, (routed || !priors.empty()) ? special.data() : nullptr,
                 priors.empty() ? nullptr : priors.data(), html, vp};
   if (g_devs.size() > 1 && offsets[n] - offsets[0] < small_batch_bytes()) {
     Picked p(pick_context());
@@ -2451,9 +2483,34 @@ int cld_valid_prefix_batch(const uint8_t* buf, const uint64_t* offsets, size_t n
 int cld_detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
                          uint32_t flags, cld_result* out, cld_chunk* chunks, size_t chunk_cap,
                          uint64_t* chunk_offsets) {
+  return detect_batch_vec(buf, offsets, n, hints, nullptr, flags, out, chunks, chunk_cap, chunk_offsets);
+}
+
+int cld_detect_batch_docflags(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
+                              const uint32_t* doc_flags, uint32_t flags, cld_result* out, int32_t* valid_prefix) {
+  if (valid_prefix && !(flags & CLD_FLAG_CHECK_UTF8)) return CLD_EINVAL;
+  if (!doc_flags)
+    return valid_prefix ? cld_detect_batch_checked(buf, offsets, n, hints, flags, out, valid_prefix)
+                        : cld_detect_batch_ex(buf, offsets, n, hints, flags, out);
+  return detect_batch_ex(buf, offsets, n, hints, flags, out, valid_prefix, doc_flags);
+}
+
+int cld_detect_batch_vec_docflags(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
+                                  const uint32_t* doc_flags, uint32_t flags, cld_result* out, cld_chunk* chunks,
+                                  size_t chunk_cap, uint64_t* chunk_offsets) {
+  return detect_batch_vec(buf, offsets, n, hints, doc_flags, flags, out, chunks, chunk_cap, chunk_offsets);
+}
+
+}  // extern "C"
+
+// cld_detect_batch_vec, and with doc_flags (nullable) cld_detect_batch_vec_docflags.
+static int detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
+                            const uint32_t* doc_flags, uint32_t flags, cld_result* out, cld_chunk* chunks,
+                            size_t chunk_cap, uint64_t* chunk_offsets) {
   if ((flags & ~(CLD_FLAG_HTML | CLD_FLAG_CHECK_UTF8 | kPublicFlags)) != 0 || !chunk_offsets || (chunk_cap > 0 && !chunks))
     return CLD_EINVAL;
   if (int rc = check_batch(buf, offsets, n, out)) return rc;
+  if (doc_flags && !doc_flags_ok(doc_flags, n)) return CLD_EINVAL;
   chunk_offsets[0] = 0;
   if (n == 0) return CLD_OK;
   if ((flags & CLD_FLAG_CHECK_UTF8) && !docs_fit_int32(offsets, n)) return CLD_EINVAL;
@@ -2462,10 +2519,12 @@ int cld_detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t n, 
   std::shared_lock<std::shared_mutex> tl(g_swap_mu);
   std::vector<uint8_t> special;
   std::vector<uint32_t> priors;
-  const bool html = (flags & CLD_FLAG_HTML) != 0;
-  if ((rc = apply_hints(buf, offsets, n, hints, html, &special, &priors))) return rc;
+  bool html = false, routed = false;
+  if ((rc = apply_hints(buf, offsets, n, hints, (flags & CLD_FLAG_HTML) != 0, doc_flags, &special, &priors, &html,
+                        &routed)))
+    return rc;
   const Batch b{buf, offsets, n, out, flags & (kCldFlags | CLD_FLAG_CHECK_UTF8),
-                (html || !priors.empty()) ? special.data() : nullptr, priors.empty() ? nullptr : priors.data(), html};
+                (routed || !priors.empty()) ? special.data() : nullptr, priors.empty() ? nullptr : priors.data(), html};
   const size_t ndev = g_devs.size();
   std::vector<std::vector<cld_chunk>> vs(ndev);
   std::vector<std::vector<int32_t>> cs(ndev);
@@ -2482,6 +2541,8 @@ int cld_detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t n, 
   }
   return total > chunk_cap ? CLD_ENOSPC : partial;
 }
+
+extern "C" {
 
 int cld_detect_batch_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
                             cld_result* d_out, void* stream) {
@@ -2532,14 +2593,21 @@ int cld_hint_boosts_device(int device, const uint8_t* d_buf, const uint64_t* d_o
   HIP_OK(hipSetDevice(d->id));
   // (no scratch of the context is used: nothing to serialise with other batches)
   HIP_OK(cld_launch_apply_hints(&d->H, d_buf, d_offsets, (int)n, d_hints, d_hint_text, hint_text_bytes,
-                                is_plain_text != 0, d_priors14, d_boosts16, nullptr,
+                                is_plain_text != 0, nullptr, d_priors14, d_boosts16, nullptr,
                                 stream ? (hipStream_t)stream : d->stream));
   return CLD_OK;
 }
 
-int cld_detect_batch_device_hints(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
-                                  uint64_t buf_bytes, const cld_hints_dev* d_hints, const uint8_t* d_hint_text,
-                                  uint64_t hint_text_bytes, cld_result* d_out, uint32_t flags, void* stream) {
+}  // extern "C"
+
+// cld_detect_batch_device_hints, and with d_doc_flags (nullable)
+// cld_detect_batch_device_docflags: the host cannot read the words, so any
+// document may be a page -- the HTML buffers are sized from buf_bytes and the
+// rewrite kernel runs (it takes the documents ApplyHints flagged).
+static int detect_batch_device_hints(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                                     uint64_t buf_bytes, const cld_hints_dev* d_hints, const uint8_t* d_hint_text,
+                                     uint64_t hint_text_bytes, const uint32_t* d_doc_flags, cld_result* d_out,
+                                     uint32_t flags, void* stream) {
   if ((flags & ~(CLD_FLAG_HTML | kPublicFlags)) != 0 || n > 0x7FFFFFFFu || (hint_text_bytes && !d_hint_text) ||
       (n > 0 && (!d_buf || !d_offsets || !d_out)))
     return CLD_EINVAL;
@@ -2550,7 +2618,7 @@ int cld_detect_batch_device_hints(int device, const uint8_t* d_buf, const uint64
   std::shared_lock<std::shared_mutex> tl(g_swap_mu);
   Device* d = g_devs[device];
   std::lock_guard<std::mutex> lk(d->mu);
-  const bool html = (flags & CLD_FLAG_HTML) != 0;
+  const bool plain = !(flags & CLD_FLAG_HTML), html = !plain || d_doc_flags;   // html: some document may be a page
   if (html && !d->T.ent_names) return CLD_EINVAL;   // tables without the HTML sections
   if ((html || d_hints) && !d->H.langtag1) return CLD_EINVAL;
   HIP_OK(hipSetDevice(d->id));
@@ -2559,20 +2627,42 @@ int cld_detect_batch_device_hints(int device, const uint8_t* d_buf, const uint64
   if (!html && !d_hints) return enqueue(d, d_buf, d_offsets, n, d_out, s, nullptr, nullptr, flags);
   if (d->d_hint_special.reserve(n) || d->d_hint_priors.reserve(16 * n)) return CLD_ENOMEM;
   HIP_OK(hipStreamWaitEvent(s, d->done, 0));        // the previous batch may still read the two buffers
-  HIP_OK(cld_launch_apply_hints(&d->H, d_buf, d_offsets, (int)n, d_hints, d_hint_text, hint_text_bytes, !html,
-                                nullptr, d->d_hint_priors, d->d_hint_special, s));
+  HIP_OK(cld_launch_apply_hints(&d->H, d_buf, d_offsets, (int)n, d_hints, d_hint_text, hint_text_bytes, plain,
+                                d_doc_flags, nullptr, d->d_hint_priors, d->d_hint_special, s));
   // (the host never learns whether any document has a prior: the langprobs always go along)
   return enqueue(d, d_buf, d_offsets, n, d_out, s, d->d_hint_special, d->d_hint_priors, flags, 0, html ? buf_bytes : 0);
 }
 
+extern "C" {
+
+int cld_detect_batch_device_hints(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                                  uint64_t buf_bytes, const cld_hints_dev* d_hints, const uint8_t* d_hint_text,
+                                  uint64_t hint_text_bytes, cld_result* d_out, uint32_t flags, void* stream) {
+  return detect_batch_device_hints(device, d_buf, d_offsets, n, buf_bytes, d_hints, d_hint_text, hint_text_bytes,
+                                   nullptr, d_out, flags, stream);
+}
+
+int cld_detect_batch_device_docflags(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                                     uint64_t buf_bytes, const cld_hints_dev* d_hints, const uint8_t* d_hint_text,
+                                     uint64_t hint_text_bytes, const uint32_t* d_doc_flags, cld_result* d_out,
+                                     uint32_t flags, void* stream) {
+  return detect_batch_device_hints(device, d_buf, d_offsets, n, buf_bytes, d_hints, d_hint_text, hint_text_bytes,
+                                   d_doc_flags, d_out, flags, stream);
+}
+
+}  // extern "C"
+
 // run_vec_shard's kernels in its order, without its copies and waits: where
 // that function goes to the host (pool regions, chunk counts, the positions of
-// the gather) the kernels of cld_vec.hip stand.
-int cld_detect_batch_device_vec(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
-                                uint64_t buf_bytes, const cld_hints_dev* d_hints, const uint8_t* d_hint_text,
-                                uint64_t hint_text_bytes, uint32_t flags, int big_regions, cld_result* d_out,
-                                cld_chunk* d_chunks, uint64_t chunk_cap, uint64_t* d_chunk_offsets,
-                                int32_t* d_valid_prefix, cld_vec_status* d_status, void* stream) {
+// the gather) the kernels of cld_vec.hip stand.  d_doc_flags (nullable):
+// cld_detect_batch_device_vec_docflags' per-document words; with them any
+// document may be a page (html below), as in detect_batch_device_hints.
+static int detect_batch_device_vec(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                                   uint64_t buf_bytes, const cld_hints_dev* d_hints, const uint8_t* d_hint_text,
+                                   uint64_t hint_text_bytes, const uint32_t* d_doc_flags, uint32_t flags,
+                                   int big_regions, cld_result* d_out, cld_chunk* d_chunks, uint64_t chunk_cap,
+                                   uint64_t* d_chunk_offsets, int32_t* d_valid_prefix, cld_vec_status* d_status,
+                                   void* stream) {
   const bool chk = (flags & CLD_FLAG_CHECK_UTF8) != 0;
   if ((flags & ~(CLD_FLAG_HTML | CLD_FLAG_CHECK_UTF8 | kPublicFlags)) != 0 || n > 0x7FFFFFFFu ||
       (d_valid_prefix && !chk) || (chunk_cap > 0 && !d_chunks) || (hint_text_bytes && !d_hint_text) ||
@@ -2584,7 +2674,7 @@ int cld_detect_batch_device_vec(int device, const uint8_t* d_buf, const uint64_t
   std::shared_lock<std::shared_mutex> tl(g_swap_mu);
   Device* d = g_devs[device];
   std::lock_guard<std::mutex> lk(d->mu);
-  const bool html = (flags & CLD_FLAG_HTML) != 0, hinted = html || d_hints;
+  const bool plain = !(flags & CLD_FLAG_HTML), html = !plain || d_doc_flags, hinted = html || d_hints;
   if (html && !d->T.ent_names) return CLD_EINVAL;   // tables without the HTML sections
   if (hinted && !d->H.langtag1) return CLD_EINVAL;
   HIP_OK(hipSetDevice(d->id));
@@ -2625,8 +2715,8 @@ int cld_detect_batch_device_vec(int device, const uint8_t* d_buf, const uint64_t
     ko = d->p_offs;
   }
   if (hinted)
-    HIP_OK(cld_launch_apply_hints(&d->H, d_buf, d_offsets, (int)n, d_hints, d_hint_text, hint_text_bytes, !html,
-                                  nullptr, V.pri, V.sp, s));
+    HIP_OK(cld_launch_apply_hints(&d->H, d_buf, d_offsets, (int)n, d_hints, d_hint_text, hint_text_bytes, plain,
+                                  d_doc_flags, nullptr, V.pri, V.sp, s));
   uint64_t* scan = (uint64_t*)(uint8_t*)d->d_sscr;
   HIP_OK(cld_launch_vec_plan(d_offsets, (int)n, mode, scan, s));
   HIP_OK(cld_launch_scan_lengths((int)n, V.pool_off, scan, s));
@@ -2652,6 +2742,29 @@ int cld_detect_batch_device_vec(int device, const uint8_t* d_buf, const uint64_t
   HIP_OK(cld_launch_vec_gather_chunks(V.pool, V.pool_off, d_chunk_offsets, (int)n, d_chunks, chunk_cap, d_status, s));
   HIP_OK(hipEventRecord(d->done, s));
   return CLD_OK;
+}
+
+extern "C" {
+
+int cld_detect_batch_device_vec(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                                uint64_t buf_bytes, const cld_hints_dev* d_hints, const uint8_t* d_hint_text,
+                                uint64_t hint_text_bytes, uint32_t flags, int big_regions, cld_result* d_out,
+                                cld_chunk* d_chunks, uint64_t chunk_cap, uint64_t* d_chunk_offsets,
+                                int32_t* d_valid_prefix, cld_vec_status* d_status, void* stream) {
+  return detect_batch_device_vec(device, d_buf, d_offsets, n, buf_bytes, d_hints, d_hint_text, hint_text_bytes, nullptr,
+                                 flags, big_regions, d_out, d_chunks, chunk_cap, d_chunk_offsets, d_valid_prefix,
+                                 d_status, stream);
+}
+
+int cld_detect_batch_device_vec_docflags(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                                         uint64_t buf_bytes, const cld_hints_dev* d_hints, const uint8_t* d_hint_text,
+                                         uint64_t hint_text_bytes, const uint32_t* d_doc_flags, uint32_t flags,
+                                         int big_regions, cld_result* d_out, cld_chunk* d_chunks, uint64_t chunk_cap,
+                                         uint64_t* d_chunk_offsets, int32_t* d_valid_prefix, cld_vec_status* d_status,
+                                         void* stream) {
+  return detect_batch_device_vec(device, d_buf, d_offsets, n, buf_bytes, d_hints, d_hint_text, hint_text_bytes,
+                                 d_doc_flags, flags, big_regions, d_out, d_chunks, chunk_cap, d_chunk_offsets,
+                                 d_valid_prefix, d_status, stream);
 }
 
 int cld_prepare_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, uint32_t flags,
