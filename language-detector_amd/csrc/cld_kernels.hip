@@ -43,8 +43,8 @@ __global__ __launch_bounds__(256) void k_vec_gather(const cld_chunk* __restrict_
 // One wave (document) per workgroup (WAVE_WPB, cld_kernels.h): a block's LDS
 // is released as soon as its own document is done, not when the slowest of
 // four is (C2 139M -> 167M docs/s; profiles/round1q_ab_wpb/).  WAVE_WPS waves
-// per SIMD: 8 blocks of 5088 B LDS per SIMD fit the CU's 160 KB (the chunk
-// tote overlays the lowered span text; raw span text, base hits and chunk
+// per SIMD: 8 blocks of 4544 B LDS per SIMD fit the CU's 160 KB (the chunk
+// tote overlays the lowered span text; raw span text, the word list and chunk
 // ids share one buffer) and 64 VGPRs hold without spills (7 -> 8 waves:
 // C2 167M -> 169M, profiles/round1q_ab_wps8/).
 #ifndef WAVE_WPS

@@ -452,10 +452,22 @@ __device__ __forceinline__ uint32_t quad_lookup(const DevTbl& t, uint32_t h) {
 // gathered at once -- the second load need not wait for the first answer --
 // so a miss costs one L2 round trip, not two.  ind: the indirect subscript,
 // bit 31 set for the second table.  Returns the matching keyvalue or 0.
+//
+// PIN (k_wave, which runs at 64 VGPRs): the two table sizes pass through an
+// empty asm with a scalar-register constraint where they are used, so the
+// size masks are computed there on the scalar unit.  Left to itself the
+// compiler computes quad2's once per document on the VALU (for the carry) and
+// keeps it in a vector register across the span loop -- a scratch spill there.
+__device__ __forceinline__ uint32_t in_sgpr(uint32_t v) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
+template <bool PIN = false>
 __device__ __forceinline__ uint32_t quad_probe(const DevTbl& q1, const DevTbl& q2, uint32_t h, uint32_t& ind) {
   const bool two = q2.size != 0 && q2.n_buckets != 0;
-  const uint4 b1 = q1.n_buckets ? gld4(q1.b + 4 * (size_t)((h + (h >> 12)) & (q1.size - 1))) : make_uint4(0, 0, 0, 0);
-  const uint4 b2 = two ? gld4(q2.b + 4 * (size_t)((h + (h >> 12)) & (q2.size - 1))) : make_uint4(0, 0, 0, 0);
+  const uint32_t m1 = (PIN ? in_sgpr(q1.size) : q1.size) - 1, m2 = (PIN ? in_sgpr(q2.size) : q2.size) - 1;
+  const uint4 b1 = q1.n_buckets ? gld4(q1.b + 4 * (size_t)((h + (h >> 12)) & m1)) : make_uint4(0, 0, 0, 0);
+  const uint4 b2 = two ? gld4(q2.b + 4 * (size_t)((h + (h >> 12)) & m2)) : make_uint4(0, 0, 0, 0);
   auto match = [](uint4 b, uint32_t key, uint32_t mask) -> uint32_t {
     if (((key ^ b.x) & mask) == 0) return b.x;
     if (((key ^ b.y) & mask) == 0) return b.y;
@@ -473,8 +485,13 @@ __device__ __forceinline__ uint32_t quad_probe(const DevTbl& q1, const DevTbl& q
   }
   return probs;
 }
+// NARROW (k_wave): the bucket subscript in 32 bits -- the table size is a u32,
+// so only the low word of h + (h >> 12) takes part, the same subscript -- and
+// the size mask stays a scalar operand instead of a 64-bit vector value.
+template <bool NARROW = false>
 __device__ __forceinline__ uint32_t octa_lookup(const DevTbl& t, uint64_t h) {
-  uint32_t sub = (uint32_t)((h + (h >> 12)) & (uint64_t)(t.size - 1));
+  const uint32_t sub = NARROW ? ((uint32_t)h + (uint32_t)(h >> 12)) & (t.size - 1)
+                              : (uint32_t)((h + (h >> 12)) & (uint64_t)(t.size - 1));
   return lookup4(t, sub, (uint32_t)(h >> 4) & t.key_mask);
 }
 __device__ __forceinline__ uint32_t ind_at(const DevTbl& t, uint32_t i) { return i < t.n_ind ? gld(t.ind + i) : 0u; }

@@ -166,18 +166,11 @@ struct Smem {
   uint8_t sn[C::DOC];                 // script number at each byte position (GetUTF8LetterScriptNum)
   uint64_t lsm[C::NM];                // letter stops: char start, scanner stops there, script != 0
   uint64_t ent[C::NM];                // rewritten HTML (cld_html.hip): lookaheads here see script 0
-  union alignas(16) {                 // one span's life: raw text -> base hits -> chunk ids
+  union alignas(16) {                 // one span's life: raw text -> word list -> chunk ids
     uint8_t sbuf[C::SB];              //   span text (raw); dead once lowered
-    struct {                          //   quad chain (quad_hits, before its base hits are written)
-      uint32_t qmark[C::QM];          //   chain entries as bits over lowered-text positions
-      uint16_t qws[C::NB];            //   word starts
-      uint16_t qchn[C::NB];           //   chain entries, in order
-    };
-    struct {                          //   base hits before expansion (hit streams -> scoring)
-      uint32_t b_ind[C::NB];
-      uint16_t b_off[C::NB];
-    };
-    struct {                          //   chunk plan, written after the base hits are expanded:
+    uint16_t wsp[C::NB + 1];          //   the span's spaces in order: word i is (wsp[i-1], wsp[i]);
+                                      //   written by quad_hits' position pass, read by both hit stages
+    struct {                          //   chunk plan, written once the hit stages are done:
       int32_t theta[C::MAXCH];        //   chunk k takes delta/distinct emissions at offset <= theta_k
       uint16_t st[3][C::MAXCH + 1];   //   first base / delta / distinct emission of chunk k
     };
@@ -189,15 +182,22 @@ struct Smem {
   union alignas(16) {                 // stage-local arrays
     uint16_t nx[CAP];                 // load: p + ScanToLetterOrSpecial(p, L - p)
     uint32_t low[CAP];                // load -> first span: lowered character starting here (pack_lowered)
-    uint16_t nxq[C::LB];              // quad hits: next quad start for a quad starting at p
-    uint16_t wsp[C::NB + 1];          // octa hits: word-ending spaces
-    struct {                          // scoring: base emissions (offset, langprob), linear order
-      uint32_t be_lp[C::NE];
+    struct {                          // hit stages -> scoring: base emissions (offset, langprob) in
+      uint32_t be_lp[C::NE];          // linear order, written by the lanes that probed (emit_base)
       uint16_t be_off[C::NE + 1];
     } e;
   } a;
-  uint16_t d_off[C::ND]; uint32_t d_ind[C::ND];   // delta hits; compacted in place to emissions
-  uint16_t x_off[C::NX]; uint32_t x_ind[C::NX];   // distinct hits; likewise
+  union alignas(16) {
+    struct {                          // octa / bigram hits -> scoring:
+      uint16_t d_off[C::ND]; uint32_t d_ind[C::ND];   // delta hits; compacted in place to emissions
+      uint16_t x_off[C::NX]; uint32_t x_ind[C::NX];   // distinct hits; likewise
+    };
+    struct {                          // quad_hits -> octa_hits' word hashes (before any d_* / x_* is written):
+      uint32_t qmark[C::QM];          //   chain entries as bits over lowered-text positions (quad_hits only)
+      uint16_t qchn[C::NB];           //   chain entries, in order (quad_hits only)
+      uint16_t nxq[C::LB];            //   GetQuadHits' step from every text position
+    };
+  };
   uint16_t E[C::MAXCH];               // cumulative base-emission count closing each chunk
   uint32_t lo[C::MAXCH];
   uint32_t ring[2][4];                // distinct boosts, latn / othr, oldest first
@@ -713,17 +713,51 @@ __device__ __forceinline__ uint32_t quad_hash_lds(const uint8_t* text, int p, in
 }
 
 // ------------------------------------------------ stage 3: hit streams
+// Base hits -> base emissions, by the lanes that probed (the first half of
+// LinearizeAll, scoreonescriptspan.cc:856-911): a kept hit's one or two
+// langprobs, zeros dropped, appended in hit order to s.a.e.  Called by all 64
+// lanes; false when the emissions pass NE (the document is handed on).
+template <int CAP>
+__device__ __forceinline__ bool emit_base(Smem<CAP>& s, const DevTbl& bo, const DevTbl& bo2, bool kept, uint32_t ind,
+                                          int off, int& eb) {
+  using C = Cfg<CAP>;
+  uint32_t l1 = 0, l2 = 0;
+  if (kept) {
+    const DevTbl* lb = &bo;
+    if (ind & 0x80000000u) { lb = &bo2; ind &= ~0x80000000u; }
+    if (ind < lb->size_one) {
+      l1 = ind_at(*lb, ind);
+    } else {
+      ind += ind - lb->size_one;
+      l1 = ind_at(*lb, ind); l2 = ind_at(*lb, ind + 1);
+      if (l1 == 0) { l1 = l2; l2 = 0; }
+    }
+  }
+  // a lane's slot from the ranks of its two flags (ballots, not a scan)
+  const uint64_t m1 = __ballot(l1 != 0), m2 = __ballot(l2 != 0);
+  const int o = eb + below(m1) + below(m2);
+  eb += __popcll(m1) + __popcll(m2);
+  if (eb > C::NE) return false;
+  if (l1) { s.a.e.be_off[o] = (uint16_t)off; s.a.e.be_lp[o] = l1; }
+  if (l2) { s.a.e.be_off[o + 1] = (uint16_t)off; s.a.e.be_lp[o + 1] = l2; }
+  return true;
+}
+
 // GetQuadHits (cldutil.cc:315-405).  The chain of quad starts is a pure
 // function of position, so next[] is computed for every byte in parallel and
 // walked by scalar code; hashes and bucket probes run per quad; the
-// "not one of the last two hits" filter is a scalar pass over the results.
+// "not one of the last two hits" filter is a scalar pass over the results,
+// and the kept hits' langprobs go straight to the base emissions (eb of
+// them; nb counts the hits, as ChunkAll wants).  The same position pass lists
+// the span's spaces for both hit stages: nw of them up to the end offset
+// (GetOctaHits' words), start the first text position.
 // Returns the end offset (reference `next`), or -1 on overflow.
 template <int CAP>
-__device__ int quad_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, int lane) {
+__device__ int quad_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, int& eb, int& start, int& nw, int lane) {
   lane = lane_here();
   using C = Cfg<CAP>;
   const uint8_t* text = s.lbuf;
-  int start = 1;
+  start = 1;
   if (text[start] == ' ') ++start;
   // The chain never jumps over a space: it enters every word at its first
   // byte, and a word's entries depend on that word alone (k_long's
@@ -731,16 +765,21 @@ __device__ int quad_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, i
   // step from there (cldutil.cc:340-400): the quad [p, p4) of four characters
   // (stopping at a space), the next chain position and whether the word's
   // chain ends at p -- packed as (p4 - p) | (next - p) << 5 | end << 10 --
-  // and the word starts.  Then one lane walks one word on those steps, one
-  // LDS read per entry, marking its entries as bits over text positions: in
-  // text order the marks are the chain.
-  uint16_t* nfo = s.a.nxq;
-  int nws = 0;
-  for (int w0 = start; w0 < limit; w0 += 64) {
+  // and the spaces, in order.  A word starts at `start` and after every space
+  // but the closing one; GetOctaHits' words (cldutil.cc:416-533) end at every
+  // space up to the end offset, the first of the padding included.  Then one
+  // lane walks one word on those steps, one LDS read per entry, marking its
+  // entries as bits over text positions: in text order the marks are the chain.
+  uint16_t* nfo = s.nxq;
+  const int last = start < limit ? limit : start;      // the end offset (below)
+  int nws = start < limit ? 1 : 0;
+  nw = 0;
+  for (int w0 = start; w0 <= last; w0 += 64) {
     const int p = w0 + lane;
     const bool in = p < limit;
-    const int pc = in ? p : start;
-    const int a1 = pc + adv_but_space(text[pc]);
+    const int pc = p <= last ? p : start;
+    const uint32_t c0 = text[pc];
+    const int a1 = pc + adv_but_space((uint8_t)c0);
     const int a2 = a1 + adv_but_space(text[a1]);
     const uint32_t c2 = text[a2];
     const int a3 = a2 + adv_but_space((uint8_t)c2);
@@ -748,15 +787,16 @@ __device__ int quad_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, i
     const int nx = a2 + adv_space_vowel((uint8_t)c2);
     const bool fin = text[a4] == ' ' || a2 >= limit || nx >= limit;
     if (in) nfo[p] = (uint16_t)((a4 - p) | ((nx - p) << 5) | (fin ? 0x400 : 0));
-    const bool isws = in && (p == start || text[p - 1] == ' ');
-    const uint64_t m = __ballot(isws);
-    if (isws) {
-      const int k = nws + below(m);
-      if (k < C::NB) s.qws[k] = (uint16_t)p;
+    const bool sp = p <= last && c0 == ' ';
+    const uint64_t m = __ballot(sp);
+    if (sp) {
+      const int k = nw + below(m);
+      if (k <= C::NB) s.wsp[k] = (uint16_t)p;
     }
-    nws += __popcll(m);
+    nw += __popcll(m);
+    nws += __popcll(__ballot(sp && p < limit - 1));    // (a word start follows)
   }
-  if (nws > C::NB) return -1;
+  if (nws > C::NB || nw > C::NB) return -1;
   if (lane < C::QM) s.qmark[lane] = 0u;
   wsync();
 #pragma unroll
@@ -764,7 +804,7 @@ __device__ int quad_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, i
     if (r * 64 >= nws) break;
     const int i = r * 64 + lane;
     if (i < nws) {
-      int p = s.qws[i];
+      int p = i == 0 ? start : s.wsp[i - 1] + 1;
       for (;;) {
         atomicOr(&s.qmark[p >> 5], 1u << (p & 31));
         const uint32_t f = nfo[p];
@@ -785,28 +825,26 @@ __device__ int quad_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, i
   }
   if (n > C::NB) return -1;
   wsync();
-  int cp[C::NR];
-#pragma unroll
-  for (int r = 0; r < C::NR; ++r) cp[r] = s.qchn[r * 64 + lane];
-  wsync();                               // (the base hits below overwrite the chain lists)
-  const int end = n == 0 ? start : limit;
+  const int end = last;                 // (a span with text has a chain: n == 0 only when start >= limit)
   // per register of chain entries, in order: hashes and probes, the repeat
   // filter (drop a hit equal to either of the last two kept hits), and the
-  // ordered compaction of the kept hits -- one register's values live at a
-  // time (the filter's state A, B and the compaction base carry over)
+  // kept hits' langprobs appended to the base emissions -- one register's
+  // values live at a time (the filter's state A, B and the counts carry over)
   uint32_t A = 0, B = 0;                  // last two kept hashes (the reference's pq0/pq1 as a set)
   int base = 0;
+  eb = 0;
 #pragma unroll
   for (int r = 0; r < C::NR; ++r) {
     if (r * 64 >= n) break;                // (uniform: registers past the chain hold nothing)
     const int i = r * 64 + lane;
     uint32_t hv = 0, pr = 0;
+    int p = 0;
     bool hit = false;
     if (i < n) {
-      const int p = cp[r];
+      p = s.qchn[i];
       hv = quad_hash_lds(text, p, (int)(nfo[p] & 31));
       uint32_t ind = 0;
-      hit = quad_probe(T.quad, T.quad2, hv, ind) != 0;
+      hit = quad_probe<true>(T.quad, T.quad2, hv, ind) != 0;
       pr = ind;
     }
     // Assume every hit is kept: then a hit's two predecessors are the previous
@@ -842,11 +880,7 @@ __device__ int quad_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, i
       B = r2 ? rdlu(hv, 63 - __builtin_clzll(r2)) : A;
       A = rdlu(hv, t1);
     }
-    if ((k >> lane) & 1) {
-      const int kk = base + below(k);
-      s.b_off[kk] = (uint16_t)cp[r];
-      s.b_ind[kk] = pr;
-    }
+    if (!emit_base<CAP>(s, T.quad, T.quad2, (k >> lane) & 1, pr, p, eb)) return -1;
     base += __popcll(k);
   }
   nb = base;
@@ -854,52 +888,44 @@ __device__ int quad_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, i
   return end;
 }
 
-// GetOctaHits (cldutil.cc:416-533): one lane per space-terminated word.
+// GetOctaHits (cldutil.cc:416-533): one lane per space-terminated word, on
+// the list of spaces quad_hits left (nw of them, the text starting at start):
+// word i ends at space i and starts after space i - 1, which the lane below
+// holds.  A word is hashed up to its first eight characters: two hops of
+// quad_hits' step record (four characters on, stopping at a space).
 template <int CAP>
-__device__ bool octa_hits(const DevTables& T, Smem<CAP>& s, int limit_next, int& nd, int& nx, int lane) {
+__device__ bool octa_hits(const DevTables& T, Smem<CAP>& s, int start, int nw, int& nd, int& nx, int lane) {
   lane = lane_here();
   using C = Cfg<CAP>;
   const uint8_t* text = s.lbuf;
-  int start = 1;
-  if (text[start] == ' ') ++start;
-  const int lim = limit_next + 1;
-  // word-ending spaces, in order
-  int nw = 0;
-  for (int w0 = start; w0 < lim; w0 += 64) {
-    const int p = w0 + lane;
-    const bool sp = p < lim && text[p] == ' ';
-    const uint64_t m = __ballot(sp);
-    if (sp) {
-      int k = nw + below(m);
-      if (k < C::NB) s.a.wsp[k] = (uint16_t)p;
-    }
-    nw += __popcll(m);
-  }
-  if (nw > C::NB) return false;
-  wsync();
+  const uint16_t* nfo = s.nxq;
   uint64_t wh[C::NR];
   int ws[C::NR], pws[C::NR];
 #pragma unroll
   for (int r = 0; r < C::NR; ++r) { wh[r] = 0; ws[r] = 0; pws[r] = 0; }
+  int e1_in = start - 1, e2_in = start - 1;     // the spaces before words r * 64 and r * 64 - 1
 #pragma unroll
   for (int r = 0; r < C::NR; ++r) {
     if (r * 64 >= nw) break;
     const int i = r * 64 + lane;
+    const int e = i < nw ? (int)s.wsp[i] : 0;
+    const int e1 = (int)wshr1((uint32_t)e, (uint32_t)e1_in);      // space i - 1
+    const int e2 = (int)wshr1((uint32_t)e1, (uint32_t)e2_in);     // space i - 2
+    e1_in = rdl(e, 63);
+    e2_in = rdl(e1, 63);
     if (i < nw) {
-      const int a = i == 0 ? start : s.a.wsp[i - 1] + 1;
-      const int e = s.a.wsp[i];
+      const int a = e1 + 1;
       ws[r] = a;
-      pws[r] = i <= 1 ? start : s.a.wsp[i - 2] + 1;
-      int we = a, q = a, cc = 0;
-      while (q < e) {
-        ++cc;
-        q += utf8_len(text[q]);
-        if (cc <= 8) we = q;
-        else break;
+      pws[r] = e2 + 1;
+      int we = a;
+      if (a < e) {
+        we += nfo[a] & 31;
+        if (we < e) we += nfo[we] & 31;
       }
       wh[r] = octa_hash40(text + a, we - a);
     }
   }
+  wsync();                                // (the probes below write d_* / x_* over the step records)
   // repeat filter (updates the pair partner even when probes miss): every word
   // takes part; assume none repeats, so a word's two predecessors are the
   // previous two lanes; from the first repeat, resolve in order.
@@ -953,9 +979,9 @@ __device__ bool octa_hits(const DevTables& T, Smem<CAP>& s, int limit_next, int&
     const bool k = (keep[r] >> lane) & 1;
     if (k) {
       const uint64_t tph = ((uint64_t)thi[r] << 32) | tlo[r];
-      if (tph != 0 && tph != wh[r]) pp = octa_lookup(T.distinctocta, pair_hash(tph, wh[r]));
-      xp = octa_lookup(T.distinctocta, wh[r]);
-      dp = octa_lookup(T.deltaocta, wh[r]);
+      if (tph != 0 && tph != wh[r]) pp = octa_lookup<true>(T.distinctocta, pair_hash(tph, wh[r]));
+      xp = octa_lookup<true>(T.distinctocta, wh[r]);
+      dp = octa_lookup<true>(T.deltaocta, wh[r]);
     }
     // a lane's slots from the ranks of its flags (ballots, not scans)
     const uint64_t mp = __ballot(pp != 0), mx = __ballot(xp != 0), md = __ballot(dp != 0);
@@ -976,13 +1002,14 @@ __device__ bool octa_hits(const DevTables& T, Smem<CAP>& s, int limit_next, int&
 
 // GetUniHits + GetBiHits (cldutil.cc:201-310), one lane per character.
 template <int CAP>
-__device__ int cjk_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, int& nd, int& nx, int lane) {
+__device__ int cjk_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, int& eb, int& nd, int& nx, int lane) {
   lane = lane_here();
   using C = Cfg<CAP>;
   const uint8_t* text = s.lbuf;
   int start = 1;
   if (text[start] == ' ') ++start;
   int b = 0;
+  eb = 0;
   uint32_t endmax = (uint32_t)start;
   for (int w0 = start; w0 < limit; w0 += 64) {
     const int p = w0 + lane;
@@ -992,12 +1019,9 @@ __device__ int cjk_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, in
       prop = uni_prop(T, text + p, len);
       endmax = (uint32_t)(p + len) > endmax ? (uint32_t)(p + len) : endmax;
     }
-    const uint64_t m = __ballot(prop > 0);
-    if (prop > 0) {
-      int k = b + below(m);
-      if (k < C::NB) { s.b_off[k] = (uint16_t)(p + len); s.b_ind[k] = (uint32_t)prop; }
-    }
-    b += __popcll(m);
+    // the unigram's langprobs straight to the base emissions, as quad_hits' hits
+    if (!emit_base<CAP>(s, T.compat, T.compat, prop > 0, (uint32_t)prop, p + len, eb)) return -1;
+    b += __popcll(__ballot(prop > 0));
   }
   if (b > C::NB) return -1;
   const int next = (int)wmax(endmax);
@@ -1070,47 +1094,18 @@ __device__ __forceinline__ void dt_add_wave(DocTote& dt, int k, int bytes, int s
 // rank arithmetic.  Linear order is the seed, then (offset, delta < distinct <
 // base, index); chunk k closes after base-type emission E_k.
 template <int CAP>
-__device__ bool score_round(const DevTables& T, Smem<CAP>& s, int ulscript, bool cjk, int nb, int nd, int nx,
+__device__ bool score_round(const DevTables& T, Smem<CAP>& s, int ulscript, bool cjk, int nb, int eb, int nd, int nx,
                             int dummy_off, int& ring_sel, int lane, const uint32_t* __restrict__ pri) {
   lane = lane_here();
   using C = Cfg<CAP>;
-  const DevTbl& bo = cjk ? T.compat : T.quad;
-  const DevTbl& bo2 = cjk ? T.compat : T.quad2;
   const DevTbl& dob = cjk ? T.deltabi : T.deltaocta;
   const DevTbl& xob = cjk ? T.distinctbi : T.distinctocta;
   const int chunksize = cjk ? kChunksizeUnis : kChunksizeQuads;
 
-  // the first 64 delta/distinct langprob gathers are issued together with the
-  // base ones, so the three table reads share one L2 round trip
+  // the first 64 delta and distinct langprob gathers are issued together: one
+  // L2 round trip (the base emissions are there already, emit_base)
   const uint32_t dpre = lane < nd ? ind_at(dob, s.d_ind[lane]) : 0u;
   const uint32_t xpre = lane < nx ? ind_at(xob, s.x_ind[lane]) : 0u;
-  // base hits -> base emissions (1 or 2 langprobs each, zeros dropped), in order
-  int eb = 0;
-  for (int j0 = 0; j0 < nb; j0 += 64) {
-    const int j = j0 + lane;
-    uint32_t l1 = 0, l2 = 0;
-    int off = 0;
-    if (j < nb) {
-      off = s.b_off[j];
-      uint32_t ind = s.b_ind[j];
-      const DevTbl* lb = &bo;
-      if (ind & 0x80000000u) { lb = &bo2; ind &= ~0x80000000u; }
-      if (ind < lb->size_one) {
-        l1 = ind_at(*lb, ind);
-      } else {
-        ind += ind - lb->size_one;
-        l1 = ind_at(*lb, ind); l2 = ind_at(*lb, ind + 1);
-        if (l1 == 0) { l1 = l2; l2 = 0; }
-      }
-    }
-    // a lane's slot from the ranks of its two flags (ballots, not a scan)
-    const uint64_t m1 = __ballot(l1 != 0), m2 = __ballot(l2 != 0);
-    const int o = eb + below(m1) + below(m2);
-    eb += __popcll(m1) + __popcll(m2);
-    if (eb > C::NE) return false;
-    if (l1) { s.a.e.be_off[o] = (uint16_t)off; s.a.e.be_lp[o] = l1; }
-    if (l2) { s.a.e.be_off[o + 1] = (uint16_t)off; s.a.e.be_lp[o + 1] = l2; }
-  }
   // delta / distinct emissions
   int ed = 0, ex = 0;
   for (int j0 = 0; j0 < nd; j0 += 64) {
@@ -1626,21 +1621,22 @@ __device__ bool detect(const DevTables& T, const uint8_t* __restrict__ g, int L,
     } else {
       const bool cjk = rt == RTypeCJK;
       lowv = false;                      // the hit stages and scoring reuse s.a
-      int nb = 0, nd = 0, nx = 0, endo;
+      int nb = 0, eb = 0, nd = 0, nx = 0, endo;
       if (cjk) {
-        endo = cjk_hits<CAP>(T, s, tb, nb, nd, nx, lane);
+        endo = cjk_hits<CAP>(T, s, tb, nb, eb, nd, nx, lane);
         mark(3);
         if (endo < 0) return false;
       } else {
-        endo = quad_hits<CAP>(T, s, tb, nb, lane);
+        int start, nw;
+        endo = quad_hits<CAP>(T, s, tb, nb, eb, start, nw, lane);
         mark(3);
         if (endo < 0) return false;
-        if (!octa_hits<CAP>(T, s, endo, nd, nx, lane)) return false;
+        if (!octa_hits<CAP>(T, s, start, nw, nd, nx, lane)) return false;
         mark(4);
       }
       if (endo < tb) return false;     // a second round would be needed (never for short documents)
       int rsel;
-      if (1 < tb && !score_round<CAP>(T, s, ulscript, cjk, nb, nd, nx, endo, rsel, lane, pri)) return false;
+      if (1 < tb && !score_round<CAP>(T, s, ulscript, cjk, nb, eb, nd, nx, endo, rsel, lane, pri)) return false;
       mark(5);
     }
     total += tb;
