@@ -88,8 +88,38 @@ typedef struct cld_result {
  * a batch that carries it takes the streamed path (a GPU pass over the text
  * in front of the kernels), never the one-launch path of request-sized
  * batches nor the coalescer's tiny groups.  The check is a GPU kernel
- * (cld_valid.hip); documents longer than INT32_MAX bytes give CLD_EINVAL. */
+ * (cld_valid.hip); documents longer than INT32_MAX bytes give CLD_EINVAL.
+ * To have such documents repaired and scored instead of rejected, see
+ * CLD_FLAG_SCRUB_UTF8 below. */
 #define CLD_FLAG_CHECK_UTF8 8u
+/* Repair instead of reject, what compact_lang_det.h:73-79 and :161-173 tell a
+ * caller of the checked entries to do with the bytes they refuse: every
+ * document is scored as the unchecked entry scores scrub(document), where
+ *   scrub(doc) = doc with each byte at an error position of the check
+ *                replaced by 0x20
+ * -- the result of the usual loop "call DetectLanguageCheckUTF8, overwrite the
+ * byte at valid_prefix_bytes with a space, call again" run to its end, in one
+ * GPU pass (an error position's verdict depends on bytes p-3 .. p+3 with bytes
+ * outside the document read as 0, and overwriting one with a space changes no
+ * other position's verdict).  The length does not change, so chunk offsets and
+ * valid prefixes still index the document as given; NUL is an error position
+ * and becomes a space; the caller's buffer is never written.  scrub(doc) is
+ * interchange-valid, so every document is scored where the reference is
+ * defined and on the parallel kernels.  Accepted wherever
+ * CLD_FLAG_CHECK_UTF8 is, as a preparation flag like it (the streamed path; per
+ * batch, never in a doc_flags word: CLD_EINVAL), applied after STRIP_EXTRAS /
+ * CSTRING and before an HTML page is rewritten or scanned for lang=.
+ * CLD_FLAG_SCRUB_UTF8 | CLD_FLAG_CHECK_UTF8 in one call is CLD_EINVAL (so is
+ * the flag in cld_detect_batch_checked), and so is a document longer than
+ * INT32_MAX bytes.  Where an entry takes a valid_prefix array with the check it
+ * takes it with this flag: it receives SpanInterchangeValid of the document as
+ * given, which equals its length iff nothing was replaced.
+ * Caution, the reference's own (compact_lang_det.h:76-79): the scrubbed text
+ * is what the detector scores, nothing more.  Text that is passed on to other
+ * software should go through a converter that turns ill-formed sequences into
+ * U+FFFD instead -- deleting bytes or turning them into spaces can create
+ * security holes there. */
+#define CLD_FLAG_SCRUB_UTF8 0x20u
 /* The reference's public result-affecting flags, with the reference's values
  * (compact_lang_det.h:343-349), accepted in the `flags` word of every batch
  * entry point and applied to every document of the batch:
@@ -140,6 +170,13 @@ const char* detect_language(const char* text);
  * (cld_valid_prefix_host) and a rejected text never reaches the GPU.
  * Otherwise detect_language(text). */
 const char* detect_language_checked(const char* text, int* valid_prefix_bytes);
+
+/* detect_language(scrub(text)) (CLD_FLAG_SCRUB_UTF8): the scrub runs on the
+ * host over a private copy (cld_scrub_utf8_host; text is not written), so an
+ * ill-formed text gets a language instead of "un".  *replaced_bytes (NULL: not
+ * wanted) receives the number of bytes replaced by a space, 0 for an
+ * interchange-valid text. */
+const char* detect_language_scrubbed(const char* text, int* replaced_bytes);
 
 /* Optional explicit initialisation.  tables_path NULL -> $CLD_MI355X_TABLES or
  * the blob shipped next to the library.  n_devices <= 0 -> all visible GPUs.
@@ -198,8 +235,8 @@ int cld_stage_cycles(int ctx, uint64_t* cycles16);
  * from concurrent callers are coalesced into one GPU batch; a batch of at
  * most 1024 documents of <= 256 bytes takes one upload, one kernel and one
  * download.  flags: 0 or CLD_FLAG_STRIP_EXTRAS / CLD_FLAG_CSTRING /
- * CLD_FLAG_CHECK_UTF8 and CLD_FLAG_SCORE_AS_QUADS / CLD_FLAG_BEST_EFFORT
- * (above).  Thread-safe. */
+ * CLD_FLAG_CHECK_UTF8 or CLD_FLAG_SCRUB_UTF8, and CLD_FLAG_SCORE_AS_QUADS /
+ * CLD_FLAG_BEST_EFFORT (above).  Thread-safe. */
 int cld_detect_batch(const uint8_t* buf, const uint64_t* offsets, size_t n,
                      cld_result* out, uint32_t flags);
 
@@ -207,7 +244,8 @@ int cld_detect_batch(const uint8_t* buf, const uint64_t* offsets, size_t n,
  * batch: `hints` is NULL or one cld_hints per document (CLDHints); flags is
  * the reference's `flags` argument -- CLD_FLAG_SCORE_AS_QUADS,
  * CLD_FLAG_BEST_EFFORT, the ignored debug flags -- plus CLD_FLAG_HTML for
- * is_plain_text = false (all documents are HTML) and CLD_FLAG_CHECK_UTF8.
+ * is_plain_text = false (all documents are HTML) and CLD_FLAG_CHECK_UTF8 or
+ * CLD_FLAG_SCRUB_UTF8.
  * Results are the same fields as cld_detect_batch.  Host buffers; blocks. */
 int cld_detect_batch_ex(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
                         uint32_t flags, cld_result* out);
@@ -220,7 +258,9 @@ int cld_detect_batch_ex(const uint8_t* buf, const uint64_t* offsets, size_t n, c
  * the "rejected" result (CLD_FLAG_CHECK_UTF8 above).  One upload serves the
  * check and the scoring.  flags: CLD_FLAG_HTML and the public CLD2 flags;
  * CLD_FLAG_STRIP_EXTRAS / CLD_FLAG_CSTRING give CLD_EINVAL, because the
- * prefixes index the documents as given.  A document longer than INT32_MAX
+ * prefixes index the documents as given, and so does CLD_FLAG_SCRUB_UTF8 (this
+ * entry rejects, that flag repairs; for the prefixes of a scrubbed batch see
+ * cld_detect_batch_docflags).  A document longer than INT32_MAX
  * bytes gives CLD_EINVAL; n == 0 CLD_OK; CLD_EIO as for cld_detect_batch. */
 int cld_detect_batch_checked(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
                              uint32_t flags, cld_result* out, int32_t* valid_prefix);
@@ -245,6 +285,37 @@ int cld_valid_prefix_batch(const uint8_t* buf, const uint64_t* offsets, size_t n
 int cld_valid_prefix_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
                             int32_t* d_valid_prefix, void* stream);
 
+/* scrub() of CLD_FLAG_SCRUB_UTF8 alone, modelled on the three above.
+ *   cld_scrub_utf8_host    one document on the host, no GPU: out[0..len)
+ *                          receives scrub(doc); out may equal doc.  Returns
+ *                          the number of replaced bytes (CLD_EINVAL if
+ *                          len > INT32_MAX or a pointer is NULL with len > 0).
+ *   cld_scrub_utf8_batch   host buffers, on GPU 0, in pieces of <= 256 MB;
+ *                          out_buf holds offsets[n] - offsets[0] bytes indexed
+ *                          like the input from its first document on (byte j
+ *                          of document i at out_buf[offsets[i] - offsets[0] +
+ *                          j]); replaced[0..n) (NULL: not wanted) the number
+ *                          of replaced bytes per document.  Blocks.
+ *   cld_scrub_utf8_device  every pointer in device memory of GPU `device`,
+ *                          enqueued on `stream` (NULL: the runtime's);
+ *                          asynchronous, uses none of the context's scratch.
+ *                          d_out is indexed by d_offsets like d_buf (bytes
+ *                          outside [d_offsets[0], d_offsets[n]) are not
+ *                          written) and must not overlap it; d_replaced
+ *                          (NULL: not wanted) as above.  Where d_out - d_buf
+ *                          is a multiple of 16 each lane of a tile stores its
+ *                          16 bytes at once, otherwise byte by byte.  The
+ *                          caller keeps documents <= INT32_MAX bytes.
+ * The input is never written.  The pass reads each byte once and writes each
+ * byte once, in the two shapes of the check.  n == 0: CLD_OK.
+ * The caution at CLD_FLAG_SCRUB_UTF8 holds here above all: the output is what
+ * the detector scores; text that goes on to other software should be
+ * converted to U+FFFD instead (compact_lang_det.h:76-79). */
+int32_t cld_scrub_utf8_host(const uint8_t* doc, size_t len, uint8_t* out);
+int cld_scrub_utf8_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, uint8_t* out_buf, int32_t* replaced);
+int cld_scrub_utf8_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n, uint8_t* d_out,
+                          int32_t* d_replaced, void* stream);
+
 /* ExtDetectLanguageSummary with a ResultChunkVector per document
  * (compact_lang_det.h:324-335): the same results as cld_detect_batch_ex plus
  * each document's chunk vector -- pieces of the document as given, in one
@@ -261,7 +332,9 @@ int cld_valid_prefix_device(int device, const uint8_t* d_buf, const uint64_t* d_
  * gets an empty vector and the call returns CLD_EIO with every other
  * document's result and vector complete.  Every document runs the sequential
  * kernel (not a high-throughput path, as in the reference).
- * CLD_FLAG_CHECK_UTF8: a rejected document gets an empty vector. */
+ * CLD_FLAG_CHECK_UTF8: a rejected document gets an empty vector.
+ * CLD_FLAG_SCRUB_UTF8: the vector is that of scrub(document), whose offsets
+ * are the document's own. */
 int cld_detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
                          uint32_t flags, cld_result* out, cld_chunk* chunks, size_t chunk_cap,
                          uint64_t* chunk_offsets);
@@ -282,7 +355,7 @@ int cld_detect_batch_device(int device, const uint8_t* d_buf, const uint64_t* d_
                             size_t n, cld_result* d_out, void* stream);
 
 /* cld_detect_batch_device with flags (preparation flags, CLD_FLAG_CHECK_UTF8
- * among them, and CLD2 flags, as for cld_detect_batch).  buf_bytes bounds
+ * or CLD_FLAG_SCRUB_UTF8 among them, and CLD2 flags, as for cld_detect_batch).  buf_bytes bounds
  * d_offsets[n] (the prepared copy is staged in a device buffer of
  * buf_bytes + n bytes).  Asynchronous like cld_detect_batch_device. */
 int cld_detect_batch_device_ex(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
@@ -318,8 +391,8 @@ int cld_hint_boosts_device(int device, const uint8_t* d_buf, const uint64_t* d_o
 /* cld_detect_batch_ex (ExtDetectLanguageSummary, compact_lang_det.h:324-335)
  * for device-resident input: d_hints is NULL or one cld_hints_dev per
  * document; flags = CLD_FLAG_HTML and the public CLD2 flags (debug flags
- * ignored).  Preparation flags, CLD_FLAG_CHECK_UTF8 included, give
- * CLD_EINVAL.  buf_bytes bounds d_offsets[n], as in
+ * ignored).  Preparation flags, CLD_FLAG_CHECK_UTF8 and CLD_FLAG_SCRUB_UTF8
+ * included, give CLD_EINVAL.  buf_bytes bounds d_offsets[n], as in
  * cld_detect_batch_device_ex.  ApplyHints runs on the GPU in front of the
  * scoring kernels; without hints and without CLD_FLAG_HTML the call is
  * cld_detect_batch_device.  Asynchronous. */
@@ -334,7 +407,8 @@ int cld_detect_batch_device_hints(int device, const uint8_t* d_buf, const uint64
  * kernels are enqueued.  d_out, d_chunk_offsets[0..n] and d_chunks are what
  * cld_detect_batch_vec gives for the same documents, hints and flags.
  *   flags        CLD_FLAG_HTML, the public CLD2 flags (debug flags ignored)
- *                and CLD_FLAG_CHECK_UTF8; CLD_FLAG_STRIP_EXTRAS /
+ *                and CLD_FLAG_CHECK_UTF8 or CLD_FLAG_SCRUB_UTF8 (both:
+ *                CLD_EINVAL); CLD_FLAG_STRIP_EXTRAS /
  *                CLD_FLAG_CSTRING and unknown bits give CLD_EINVAL (chunk
  *                offsets and prefixes index the documents as given).
  *   d_hints      NULL or one cld_hints_dev per document (their texts in
@@ -346,6 +420,10 @@ int cld_detect_batch_device_hints(int device, const uint8_t* d_buf, const uint64
  *                cld_detect_batch_checked gives it.  d_valid_prefix without
  *                the flag is CLD_EINVAL.  The caller keeps documents
  *                <= INT32_MAX bytes.
+ *   SCRUB_UTF8   every document is scored as scrub(document), hints' lang=
+ *                scan included; d_valid_prefix as with CHECK_UTF8 (of the
+ *                document as given: its length iff nothing was replaced), and
+ *                d_status->rejected_docs counts the repaired documents.
  *   capacity     d_chunk_offsets always holds the true totals, d_chunks
  *                receives the first chunk_cap chunks and nothing is written
  *                past d_chunks + chunk_cap.  chunk_cap 0 with d_chunks NULL is
@@ -371,7 +449,8 @@ int cld_detect_batch_device_hints(int device, const uint8_t* d_buf, const uint64
 typedef struct cld_vec_status {   /* 16 bytes, written by the last kernel of the call */
   uint64_t total_chunks;          /* = d_chunk_offsets[n]; > chunk_cap means the CLD_ENOSPC case */
   uint32_t failed_docs;           /* documents whose vector outgrew its pool region (above)    */
-  uint32_t rejected_docs;         /* CLD_FLAG_CHECK_UTF8: documents not interchange-valid      */
+  uint32_t rejected_docs;         /* CLD_FLAG_CHECK_UTF8 / SCRUB_UTF8: documents not           */
+                                  /* interchange-valid (rejected, or repaired and scored)      */
 } cld_vec_status;
 
 int cld_detect_batch_device_vec(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
@@ -403,7 +482,8 @@ int cld_detect_batch_device_vec(int device, const uint8_t* d_buf, const uint64_t
  *
  * Host entries: a word with any bit outside CLD_FLAG_HTML |
  * CLD_FLAG_SCORE_AS_QUADS | CLD_FLAG_BEST_EFFORT | CLD_FLAG_DEBUG_MASK
- * (CLD_FLAG_STRIP_EXTRAS, CLD_FLAG_CSTRING, CLD_FLAG_CHECK_UTF8, unknown bits)
+ * (CLD_FLAG_STRIP_EXTRAS, CLD_FLAG_CSTRING, CLD_FLAG_CHECK_UTF8,
+ * CLD_FLAG_SCRUB_UTF8, unknown bits)
  * gives CLD_EINVAL, before any GPU work.  Words that are all zero cost
  * nothing: the call is then cld_detect_batch_ex's.  Otherwise the batch
  * carries one routing byte per document to the GPU (as a hinted batch does),
@@ -415,6 +495,9 @@ int cld_detect_batch_device_vec(int device, const uint8_t* d_buf, const uint64_t
  *                                  in flags also cld_detect_batch_checked:
  *                                  valid_prefix (NULL: not wanted; n entries)
  *                                  receives SpanInterchangeValid per document.
+ *                                  With CLD_FLAG_SCRUB_UTF8 it receives the
+ *                                  same (of the documents as given) and every
+ *                                  document is scored.
  *                                  valid_prefix without the flag: CLD_EINVAL.
  *   cld_detect_batch_vec_docflags  cld_detect_batch_vec, with its errors
  *                                  (chunk_offsets NULL, chunk_cap > 0 without
@@ -429,7 +512,7 @@ int cld_detect_batch_vec_docflags(const uint8_t* buf, const uint64_t* offsets, s
  * cld_detect_batch_device_vec with d_doc_flags[n] in device memory of GPU
  * `device`; every other argument, the asynchrony and the errors are theirs
  * (flags: CLD_FLAG_HTML and the public CLD2 flags; the vector entry also
- * CLD_FLAG_CHECK_UTF8).  d_doc_flags == NULL forwards to them.
+ * CLD_FLAG_CHECK_UTF8 or CLD_FLAG_SCRUB_UTF8).  d_doc_flags == NULL forwards to them.
  * The host never reads the words, so it cannot reject one: the ApplyHints
  * kernel (cld_hints.hip) masks each word to CLD_FLAG_HTML |
  * CLD_FLAG_SCORE_AS_QUADS | CLD_FLAG_BEST_EFFORT and ignores every other bit,

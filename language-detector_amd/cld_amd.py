@@ -10,6 +10,10 @@ Mirrors the reference's caller-facing interface for this path:
                                           (compact_lang_det.cc:317-355) -> (results, valid prefixes)
   detect_language_checked(text)           DetectLanguageCheckUTF8 (compact_lang_det.cc:44-56)
   valid_prefix_batch(docs)                SpanInterchangeValid per document, as a GPU kernel
+  detect_batch(docs, flags=FLAG_SCRUB_UTF8)   ill-formed bytes repaired (each error position of the
+                                          check becomes a space) and every document scored
+  scrub_utf8_batch(docs)                  that repair alone, as a GPU kernel -> (buffer, replaced)
+  detect_language_scrubbed(text)          the repair on the host, then detect_language
 There is no CPU fallback: if the HIP library or a GPU is missing, calls raise.
 """
 import ctypes
@@ -28,6 +32,7 @@ FLAG_STRIP_EXTRAS = 1      # include/cld_mi355x.h CLD_FLAG_STRIP_EXTRAS
 FLAG_CSTRING = 2           # include/cld_mi355x.h CLD_FLAG_CSTRING
 FLAG_HTML = 4              # include/cld_mi355x.h CLD_FLAG_HTML (cld_detect_batch_ex)
 FLAG_CHECK_UTF8 = 8        # include/cld_mi355x.h CLD_FLAG_CHECK_UTF8: documents that are not interchange-valid are not scored
+FLAG_SCRUB_UTF8 = 0x20     # include/cld_mi355x.h CLD_FLAG_SCRUB_UTF8: error positions of the check become 0x20, every document is scored
 VALID_TILE = 1024          # csrc/cld_kernels.h kValidTile: the check's tile (documents over VALID_SHORT_MAX bytes)
 VALID_SHORT_MAX = 256      # csrc/cld_kernels.h kValidShortMax
 FLAG_SCORE_AS_QUADS = 0x0100   # CLD_FLAG_SCORE_AS_QUADS = kCLDFlagScoreAsQuads (compact_lang_det.h:343)
@@ -53,7 +58,8 @@ EXPORTS = ("detect_language", "cld_init", "cld_init_device", "cld_shutdown", "cl
            "cld_valid_prefix_device", "detect_language_checked", "cld_hint_boosts_device",
            "cld_detect_batch_device_hints", "cld_detect_batch_device_vec", "cld_detect_batch_docflags",
            "cld_detect_batch_vec_docflags", "cld_detect_batch_device_docflags",
-           "cld_detect_batch_device_vec_docflags")
+           "cld_detect_batch_device_vec_docflags", "cld_scrub_utf8_host", "cld_scrub_utf8_batch",
+           "cld_scrub_utf8_device", "detect_language_scrubbed")
 CHUNK_DTYPE = np.dtype([("offset", "<i4"), ("bytes", "<i4"), ("lang1", "<u2"), ("pad", "<u2")])   # cld_chunk
 
 
@@ -199,6 +205,12 @@ def lib():
                                                            ctypes.c_int, vp, vp, u64, vp, vp, vp, vp]
         L.detect_language_checked.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
         L.detect_language_checked.restype = ctypes.c_char_p
+        L.cld_scrub_utf8_host.argtypes = [vp, sz, vp]
+        L.cld_scrub_utf8_host.restype = ctypes.c_int32
+        L.cld_scrub_utf8_batch.argtypes = [vp, vp, sz, vp, vp]
+        L.cld_scrub_utf8_device.argtypes = [ctypes.c_int, vp, vp, sz, vp, vp, vp]
+        L.detect_language_scrubbed.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
+        L.detect_language_scrubbed.restype = ctypes.c_char_p
         _lib = L
     return _lib
 
@@ -305,7 +317,8 @@ def pack(docs):
 def detect_batch(docs=None, buf=None, offsets=None, flags=0, out=None):
     """One DetectLanguageSummaryV2 per document; flags = FLAG_STRIP_EXTRAS | FLAG_CSTRING
     prepares each text as POST / does before detecting (handlers.go:150-151);
-    FLAG_SCORE_AS_QUADS / FLAG_BEST_EFFORT are CLD2's own flags.  out: an
+    FLAG_CHECK_UTF8 rejects and FLAG_SCRUB_UTF8 repairs what is not interchange-valid
+    UTF-8 (one of the two); FLAG_SCORE_AS_QUADS / FLAG_BEST_EFFORT are CLD2's own flags.  out: an
     existing contiguous RESULT_DTYPE array of n entries to fill (a caller that
     reuses its result buffer, as a service would), else a new one."""
     if docs is not None:
@@ -331,7 +344,8 @@ def detect_batch(docs=None, buf=None, offsets=None, flags=0, out=None):
 def detect_batch_ex(docs=None, buf=None, offsets=None, hints=None, html=False, flags=0):
     """ExtDetectLanguageSummary per document (compact_lang_det.h:324-335):
     html=True scores every document as HTML (is_plain_text = false); hints is
-    None or one Hints per document; flags: FLAG_SCORE_AS_QUADS / FLAG_BEST_EFFORT / FLAG_CHECK_UTF8."""
+    None or one Hints per document; flags: FLAG_SCORE_AS_QUADS / FLAG_BEST_EFFORT and
+    FLAG_CHECK_UTF8 or FLAG_SCRUB_UTF8."""
     if docs is not None:
         buf, offsets = pack(docs)
     buf = np.ascontiguousarray(buf, dtype=np.uint8)
@@ -358,7 +372,7 @@ def detect_batch_ex(docs=None, buf=None, offsets=None, hints=None, html=False, f
 def detect_batch_vec(docs=None, buf=None, offsets=None, hints=None, html=False, chunk_cap=None, flags=0):
     """ExtDetectLanguageSummary with a ResultChunkVector per document:
     (results, chunks [CHUNK_DTYPE], chunk_offsets[n+1]); document i's vector is
-    chunks[chunk_offsets[i]:chunk_offsets[i+1]]."""
+    chunks[chunk_offsets[i]:chunk_offsets[i+1]].  flags as for detect_batch_ex."""
     if docs is not None:
         buf, offsets = pack(docs)
     buf = np.ascontiguousarray(buf, dtype=np.uint8)
@@ -441,7 +455,8 @@ def detect_batch_device_vec(device, d_buf_ptr, d_offsets_ptr, n, buf_bytes, d_ou
     the stream.  d_out_ptr: RESULT_DTYPE[n], d_chunk_offsets_ptr: uint64[n + 1], d_status_ptr: one
     VEC_STATUS_DTYPE record, d_chunks_ptr: CHUNK_DTYPE[chunk_cap] (None with chunk_cap 0: the
     sizing pass -- read total_chunks from the status, allocate, call again).  flags: FLAG_HTML,
-    FLAG_CHECK_UTF8 (d_valid_prefix_ptr: int32[n] or None), FLAG_SCORE_AS_QUADS, FLAG_BEST_EFFORT.
+    FLAG_CHECK_UTF8 or FLAG_SCRUB_UTF8 (d_valid_prefix_ptr: int32[n] or None; rejected_docs of the
+    status counts the rejected / the repaired documents), FLAG_SCORE_AS_QUADS, FLAG_BEST_EFFORT.
     Documents counted in failed_docs (summary_lang == LANG_FAILED, empty vector) are redone
     with big_regions=True or through detect_batch_vec."""
     rc = lib().cld_detect_batch_device_vec(device, d_buf_ptr, d_offsets_ptr, n, buf_bytes, d_hints_ptr,
@@ -466,7 +481,8 @@ def detect_batch_docflags(docs=None, buf=None, offsets=None, hints=None, doc_fla
     """cld_detect_batch_docflags: detect_batch_ex with is_plain_text and CLD2's flags per
     document -- document i is scored with flags | doc_flags[i] (FLAG_HTML, FLAG_SCORE_AS_QUADS,
     FLAG_BEST_EFFORT; doc_flags: uint32[n] or None).  flags as for detect_batch_ex; with
-    FLAG_CHECK_UTF8 and valid_prefix=True -> (results, valid_prefix int32[n])."""
+    FLAG_CHECK_UTF8 or FLAG_SCRUB_UTF8 and valid_prefix=True -> (results, valid_prefix int32[n]),
+    the prefixes of the documents as given."""
     if docs is not None:
         buf, offsets = pack(docs)
     buf = np.ascontiguousarray(buf, dtype=np.uint8)
@@ -577,6 +593,53 @@ def detect_language_checked(text):
     vp = ctypes.c_int(0)
     code = lib().detect_language_checked(b, ctypes.byref(vp)).decode()
     return code, vp.value
+
+
+def detect_language_scrubbed(text):
+    """detect_language of the text with every error position of the UTF-8 check replaced
+    by a space (FLAG_SCRUB_UTF8, on the host) -> (ISO code, replaced_bytes)."""
+    b = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+    r = ctypes.c_int(0)
+    code = lib().detect_language_scrubbed(b, ctypes.byref(r)).decode()
+    return code, r.value
+
+
+def scrub_utf8_host(doc):
+    """scrub(doc) on the host (cld_scrub_utf8_host, no GPU) -> (bytes, replaced): doc with each
+    byte at an error position of the interchange-valid check replaced by 0x20."""
+    b = doc.encode("utf-8") if isinstance(doc, str) else bytes(doc)
+    out = ctypes.create_string_buffer(max(len(b), 1))
+    rc = lib().cld_scrub_utf8_host(b, len(b), out)
+    if rc < 0:
+        raise CldError("cld_scrub_utf8_host failed: %d" % rc)
+    return out.raw[:len(b)], rc
+
+
+def scrub_utf8_batch(docs=None, buf=None, offsets=None, replaced=True):
+    """scrub() per document on the GPU (cld_scrub_utf8_batch) -> (uint8 buffer of
+    offsets[n] - offsets[0] bytes, indexed like the input from its first document on,
+    replaced int32[n] or None).  The input is not written."""
+    if docs is not None:
+        buf, offsets = pack(docs)
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    out = np.zeros(int(offsets[n] - offsets[0]) if n > 0 else 0, dtype=np.uint8)
+    cnt = np.zeros(n, dtype=np.int32) if replaced else None
+    bptr = buf.ctypes.data if buf.size else ctypes.addressof(ctypes.c_uint8(0))
+    optr = out.ctypes.data if out.size else ctypes.addressof(ctypes.c_uint8(0))
+    rc = lib().cld_scrub_utf8_batch(bptr, offsets.ctypes.data, n, optr, cnt.ctypes.data if replaced else None)
+    if rc != 0:
+        raise CldError("cld_scrub_utf8_batch failed: %d" % rc)
+    return out, cnt
+
+
+def scrub_utf8_device(device, d_buf_ptr, d_offsets_ptr, n, d_out_ptr, d_replaced_ptr=None, stream_ptr=None):
+    """cld_scrub_utf8_device: every pointer in device memory (d_out indexed like d_buf,
+    d_replaced int32[n] or None); asynchronous on the stream."""
+    rc = lib().cld_scrub_utf8_device(device, d_buf_ptr, d_offsets_ptr, n, d_out_ptr, d_replaced_ptr, stream_ptr)
+    if rc != 0:
+        raise CldError("cld_scrub_utf8_device failed: %d" % rc)
 
 
 def valid_prefix_host(doc):

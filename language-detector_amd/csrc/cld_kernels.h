@@ -167,6 +167,14 @@ constexpr int kValidShortMax = 256;
 constexpr int kValidTile = 1024;
 hipError_t cld_launch_valid_prefix(const uint8_t* buf, const uint64_t* offs, int n, int32_t* valid_prefix,
                                    uint64_t bytes_hint, hipStream_t s);
+// CLD_FLAG_SCRUB_UTF8 / cld_scrub_utf8_*: out[offs[i] + j] = byte j of document
+// i with every error position of the check replaced by 0x20 (out is indexed
+// like buf and does not overlap it; one 16-byte store per lane of a tile where
+// out - buf is a multiple of 16, byte stores otherwise).  replaced[i]
+// (nullable): the number of replaced bytes; valid_prefix[i] (nullable): the
+// first of them, SpanInterchangeValid of the document as given.
+hipError_t cld_launch_scrub(const uint8_t* buf, const uint64_t* offs, int n, uint8_t* out, int32_t* replaced,
+                            int32_t* valid_prefix, uint64_t bytes_hint, hipStream_t s);
 // CLD_FLAG_CHECK_UTF8: len[i] = document i's length when valid_prefix[i] says
 // the whole of it is valid, else 0; the valid documents copied to out at
 // out_offs (the scan of len); the reference's "rejected" result written over

@@ -892,7 +892,7 @@ LNG_NS_INL int next_span(const DevTables& T, const DocView& dv, Slot& S, uint8_t
     }
     const bool lead = cls_lead(cw);
     const int n = cls_n(cw);
-    bool brk = false, ok = false, foreign = false;
+    bool brk = false, ok = false, foreign = false, stalec = false;
     if (lead) {
       const int sc = cls_sn(cw);
       if (sc != ss && sc != inherited) {
@@ -906,6 +906,16 @@ LNG_NS_INL int next_span(const DevTables& T, const DocView& dv, Slot& S, uint8_t
           if (dv.hf && x + n < L && gld(dv.hf + x + n)) sc2 = 0;   // onto a rewritten HTML entity: the raw '&'
           brk = sc2 != common && sc2 != ss;
         }
+      }
+      // rewritten HTML: dropped '&'s right before this letter (hflag bit 1).  After a single
+      // letter of another script the reference's letters loop meets them with that letter's
+      // script still in hand, and the script of this letter then decides whether the span breaks
+      // at the last '&' (getonescriptspan.cc:876-931): the sequential span source scans such a page
+      if (!brk && dv.hf && x > q && sc != common && sc != ss && (gld(dv.hf + x) & 2)) {
+        int pc = x - 1;
+        while (pc > q && (dv.p[pc] & 0xC0) == 0x80) --pc;
+        const int scp = script_num(T, dv, pc);
+        stalec = scp != 0 && scp != common && scp != ss && scp != inherited;
       }
       if ((cw >> 20) & 1) {
         if (sc == ss || sc == inherited) ok = true;
@@ -929,6 +939,7 @@ LNG_NS_INL int next_span(const DevTables& T, const DocView& dv, Slot& S, uint8_t
     const uint64_t stopm = Em | Hm | Sm;
     const int stop = stopm ? __builtin_ctzll(stopm) : 64;
     const bool act = lane <= stop;
+    if (stalec && prev_run && act) bad = 1;              // (reached by this span's letters loop)
     const bool hard_here = lane == stop && ((Hm >> lane) & 1);
     const bool out_chr = act && chr && !cutc;
     if (out_chr && cls_nolow(cw)) bad = 1;

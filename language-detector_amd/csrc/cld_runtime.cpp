@@ -96,6 +96,31 @@ bool docs_fit_int32(const uint64_t* offsets, size_t n) {
   return bad == 0;
 }
 
+// CLD_FLAG_CHECK_UTF8 | CLD_FLAG_SCRUB_UTF8 in one call: reject-and-repair is a contradiction.
+bool utf8_flags_ok(uint32_t flags) {
+  return (flags & (CLD_FLAG_CHECK_UTF8 | CLD_FLAG_SCRUB_UTF8)) != (CLD_FLAG_CHECK_UTF8 | CLD_FLAG_SCRUB_UTF8);
+}
+
+// scrub(doc) (cld_valid_rule.h): out[p] = 0x20 at every error position, doc[p]
+// elsewhere; out may be doc.  Returns the number of replaced bytes; *first
+// (nullable): the first of them, len if none.
+size_t scrub_host(const uint8_t* doc, size_t len, uint8_t* out, size_t* first) {
+  uint32_t l1 = 0, l2 = 0, l3 = 0;              // char_len at p-1, p-2, p-3, of the bytes as given
+  uint32_t c = len > 0 ? doc[0] : 0, n1 = len > 1 ? doc[1] : 0, n2 = len > 2 ? doc[2] : 0;
+  size_t replaced = 0, f = len;
+  for (size_t p = 0; p < len; ++p) {            // (every byte is read before its position is written)
+    const uint32_t n3 = p + 3 < len ? doc[p + 3] : 0;
+    const uint32_t l0 = cld::valid::char_len(c, n1, n2, n3);
+    const bool err = cld::valid::is_error(c, l0, l1, l2, l3);
+    out[p] = err ? (uint8_t)0x20 : (uint8_t)c;
+    if (err && replaced++ == 0) f = p;
+    l3 = l2; l2 = l1; l1 = l0;
+    c = n1; n1 = n2; n2 = n3;
+  }
+  if (first) *first = f;
+  return replaced;
+}
+
 // The argument checks every host batch entry point shares.
 int check_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, const void* out) {
   if (n > 0 && (!buf || !offsets || !out)) return CLD_EINVAL;
@@ -493,11 +518,13 @@ struct Device {
   DevBuf<uint32_t> d_hint_priors;
   // CLD_FLAG_CHECK_UTF8 (cld_valid.hip): valid prefixes, and the prepared batch in which a rejected
   // document is empty.  p_buf / p_offs: where enqueue_prepare left the prepared batch (d_sbuf or d_cbuf);
-  // chk_offs / chk_vp: the offsets and prefixes the check ran on (enqueue_fixup reads them)
+  // chk_offs / chk_vp: the offsets and prefixes the check ran on (enqueue_fixup reads them).
+  // CLD_FLAG_SCRUB_UTF8: d_cbuf holds the scrubbed copy, indexed by the offsets the step was given
+  // (p_offs; p_base: their first document's offset where the caller said so, the bias of p_buf)
   DevBuf<int32_t> d_vp;
   DevBuf<uint8_t> d_cbuf;
   DevBuf<uint64_t> d_coffs;
-  const uint8_t* p_buf = nullptr; const uint64_t* p_offs = nullptr;
+  const uint8_t* p_buf = nullptr; const uint64_t* p_offs = nullptr; uint64_t p_base = 0;
   const uint64_t* chk_offs = nullptr; const int32_t* chk_vp = nullptr;
   cld_batch_stats last{};
   uint64_t last_n = 0;
@@ -765,7 +792,8 @@ int init_device(Device* d) {
 
 constexpr uint32_t kStripFlags = CLD_FLAG_STRIP_EXTRAS | CLD_FLAG_CSTRING;
 // flags that put a preparation step in front of the kernels (such batches take the streamed path)
-constexpr uint32_t kPrepFlags = kStripFlags | CLD_FLAG_CHECK_UTF8;
+constexpr uint32_t kUtf8Flags = CLD_FLAG_CHECK_UTF8 | CLD_FLAG_SCRUB_UTF8;   // reject or repair: never both
+constexpr uint32_t kPrepFlags = kStripFlags | kUtf8Flags;
 // the reference's public flags the kernels apply; its debug-output flags are accepted and ignored
 constexpr uint32_t kCldFlags = CLD_FLAG_SCORE_AS_QUADS | CLD_FLAG_BEST_EFFORT;
 constexpr uint32_t kPublicFlags = kCldFlags | CLD_FLAG_DEBUG_MASK;
@@ -813,21 +841,34 @@ uint32_t heavy_kb() {
 //    above left: valid prefixes into vp (n entries; nullptr: d_vp), then a copy
 //    in d_cbuf / d_coffs in which every rejected document is empty, so no
 //    scoring kernel reads an ill-formed byte.  enqueue_fixup, after the
-//    kernels, gives those documents the reference's "rejected" result.
+//    kernels, gives those documents the reference's "rejected" result;
+//  * CLD_FLAG_SCRUB_UTF8, in its place: the scrubbed copy in d_cbuf under the
+//    offsets the step above left (no lengths, no scan, and no fixup afterwards:
+//    nothing is rejected); valid prefixes into vp only where vp is given.
+//    base: offs[0] where the buffer is biased by it (the streamed path's
+//    chunks; the strip step's output starts at 0 either way): d->p_base.
 int enqueue_prepare(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, uint64_t cap_bytes,
-                    uint32_t flags, hipStream_t s, int32_t* vp = nullptr) {
+                    uint32_t flags, hipStream_t s, int32_t* vp = nullptr, uint64_t base = 0) {
   HIP_OK(hipStreamWaitEvent(s, d->done, 0));   // the previous batch may still read d_sbuf
   if (d->d_sscr.reserve(cld_strip_scratch_bytes((int)n))) return CLD_ENOMEM;
   const uint8_t* src = buf;
   const uint64_t* so = offs;
-  if ((flags & kStripFlags) || !(flags & CLD_FLAG_CHECK_UTF8)) {   // (neither flag: a plain copy, cld_prepare_batch)
+  d->p_base = 0;
+  if ((flags & kStripFlags) || !(flags & kUtf8Flags)) {   // (neither flag: a plain copy, cld_prepare_batch)
     if (d->d_sbuf.reserve(std::max<size_t>(cap_bytes + n, 1)) || d->d_soffs.reserve(n + 1)) return CLD_ENOMEM;
     HIP_OK(cld_launch_strip_offsets(buf, offs, (int)n, flags & kStripFlags, d->d_soffs, d->d_sscr, s));
     HIP_OK(cld_launch_strip_write(buf, offs, (int)n, flags & kStripFlags, d->d_soffs, d->d_sbuf, s));
     src = d->d_sbuf;
     so = d->d_soffs;
+    base = 0;
   }
-  if (flags & CLD_FLAG_CHECK_UTF8) {
+  if (flags & CLD_FLAG_SCRUB_UTF8) {
+    if (d->d_cbuf.reserve(std::max<size_t>(cap_bytes + n, 1))) return CLD_ENOMEM;
+    uint8_t* cb = d->d_cbuf;
+    HIP_OK(cld_launch_scrub(src, so, (int)n, cb - base, nullptr, vp, cap_bytes + n, s));
+    src = cb - base;
+    d->p_base = base;
+  } else if (flags & CLD_FLAG_CHECK_UTF8) {
     if (!vp) {
       if (d->d_vp.reserve(std::max<size_t>(n, 1))) return CLD_ENOMEM;
       vp = d->d_vp;
@@ -1308,7 +1349,7 @@ int run_host_stream(Device* d, const Batch& b, cld_batch_stats* st_out) {
     if (!r && b.special) r = h.h_sp.reserve(max_m);
     if (!r && b.priors) r = h.d_pri.reserve(16 * max_m);
     if (!r && b.priors) r = h.h_pri.reserve(16 * max_m);
-    if (!r && (b.flags & CLD_FLAG_CHECK_UTF8)) r = h.d_vp.reserve(std::max<size_t>(max_m, 1));
+    if (!r && ((b.flags & CLD_FLAG_CHECK_UTF8) || b.vp_out)) r = h.d_vp.reserve(std::max<size_t>(max_m, 1));
     if (!r && b.vp_out) r = h.h_vp.reserve(std::max<size_t>(max_m, 1));
     if (r) return r;
   }
@@ -1374,10 +1415,15 @@ int run_host_stream(Device* d, const Batch& b, cld_batch_stats* st_out) {
       }
     }
     const bool prep = (b.flags & kPrepFlags) != 0, chk = (b.flags & CLD_FLAG_CHECK_UTF8) != 0;
-    if (prep && (rc = enqueue_prepare(d, kbuf, h.d_offs, m, bytes, b.flags, d->stream, chk ? h.d_vp : nullptr))) break;
-    // (the prepared batch's offsets start at 0: HTML pages are rewritten with base 0)
+    // (the scrub only reports prefixes where the caller wants them)
+    if (prep && (rc = enqueue_prepare(d, kbuf, h.d_offs, m, bytes, b.flags, d->stream,
+                                      (chk || b.vp_out) ? h.d_vp : nullptr, base)))
+      break;
+    // (the checked or stripped batch's offsets start at 0: HTML pages are rewritten with base 0;
+    // the scrubbed copy of unstripped text keeps the chunk's own offsets)
     rc = enqueue(d, prep ? d->p_buf : kbuf, prep ? d->p_offs : h.d_offs, m, h.d_out, d->stream,
-                 b.special ? h.d_sp : nullptr, (b.special && b.priors) ? h.d_pri : nullptr, b.flags, prep ? 0 : base,
+                 b.special ? h.d_sp : nullptr, (b.special && b.priors) ? h.d_pri : nullptr, b.flags,
+                 prep ? d->p_base : base,
                  (b.special && b.html) ? bytes : 0, d->d_ctrs + c * kCtrSlots, long_hint);
     if (rc == CLD_OK && chk) rc = enqueue_fixup(d, h.d_out, m, d->stream);
     if (rc) break;
@@ -1681,15 +1727,16 @@ int run_vec_shard(Device* d, const Batch& b, std::vector<cld_chunk>* chunks, std
     // CLD_FLAG_CHECK_UTF8: the kernels get the prepared batch, in which a
     // rejected document is empty (a valid one is a copy: its chunk offsets
     // index the document as given either way)
+    // CLD_FLAG_SCRUB_UTF8: they get the scrubbed copy under the same offsets
     const bool chk = (b.flags & CLD_FLAG_CHECK_UTF8) != 0;
     const uint8_t* kb = V.in - base;
     const uint64_t* ko = V.offs;
     uint64_t kbase = base;
-    if (chk) {
-      if (int rc = enqueue_prepare(d, kb, ko, m, bytes, CLD_FLAG_CHECK_UTF8, s)) return rc;
+    if (b.flags & kUtf8Flags) {
+      if (int rc = enqueue_prepare(d, kb, ko, m, bytes, b.flags & kUtf8Flags, s, nullptr, base)) return rc;
       kb = d->p_buf;
       ko = d->p_offs;
-      kbase = 0;
+      kbase = d->p_base;
     }
     {
       if (d->d_requeue.reserve(m) || d->d_requeue2.reserve(m) || d->d_lsorted.reserve(m) || d->d_lkey.reserve(m))
@@ -2278,10 +2325,10 @@ void cld_shutdown(void) {
 }
 
 int cld_detect_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, cld_result* out, uint32_t flags) {
-  if ((flags & ~(kPrepFlags | kPublicFlags)) != 0) return CLD_EINVAL;
+  if ((flags & ~(kPrepFlags | kPublicFlags)) != 0 || !utf8_flags_ok(flags)) return CLD_EINVAL;
   if (int rc = check_batch(buf, offsets, n, out)) return rc;
   if (n == 0) return CLD_OK;
-  if ((flags & CLD_FLAG_CHECK_UTF8) && !docs_fit_int32(offsets, n)) return CLD_EINVAL;
+  if ((flags & kUtf8Flags) && !docs_fit_int32(offsets, n)) return CLD_EINVAL;
   int rc = cld_init(nullptr, 0);
   if (rc) return rc;
   std::shared_lock<std::shared_mutex> tl(g_swap_mu);
@@ -2321,7 +2368,7 @@ namespace {
 // *any_html: some document is HTML; *routed: some routing byte is not zero.
 int apply_hints(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints, bool html,
                 const uint32_t* doc_flags, std::vector<uint8_t>* special, std::vector<uint32_t>* priors,
-                bool* any_html, bool* routed) {
+                bool* any_html, bool* routed, bool scrub = false) {
   special->assign(n, html ? kSpecialHtml : 0);
   bool some_html = html, some_bits = html;
   if (doc_flags)
@@ -2343,11 +2390,21 @@ int apply_hints(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld
                                                            (n + 4095) / 4096));
   auto work = [&](size_t lo, size_t hi) {
     bool a = false;
+    std::vector<uint8_t> head;
     for (size_t i = lo; i < hi; ++i) {
       int16_t p[cld::kMaxPriors];
       const bool page = ((*special)[i] & kSpecialHtml) != 0;   // (the lang= scan of this document's first 8 KB)
-      const int k = cld::hint_priors(g_tab.hints, buf + offsets[i], offsets[i + 1] - offsets[i], !page,
-                                     hints ? hints + i : nullptr, p);
+      const uint8_t* doc = buf + offsets[i];
+      size_t len = offsets[i + 1] - offsets[i];
+      if (scrub && page) {
+        // the lang= scan reads the first 8 KB of the text that is scored: the scrubbed one (a byte of
+        // it depends on the three after it, so three more go through the pass and are not looked at)
+        len = std::min<size_t>(len, (8u << 10) + 3);
+        head.resize(len);
+        scrub_host(doc, len, head.data(), nullptr);
+        doc = head.data();
+      }
+      const int k = cld::hint_priors(g_tab.hints, doc, len, !page, hints ? hints + i : nullptr, p);
       if (k <= 0) continue;
       uint32_t* o = priors->data() + 16 * i;
       cld::hint_boosts(g_tab.hints, p, k, o);
@@ -2384,20 +2441,20 @@ static int detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t 
 // doc_flags (nullable): cld_detect_batch_docflags' per-document words.
 static int detect_batch_ex(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
                            uint32_t flags, cld_result* out, int32_t* vp, const uint32_t* doc_flags = nullptr) {
-  if ((flags & ~(CLD_FLAG_HTML | CLD_FLAG_CHECK_UTF8 | kPublicFlags)) != 0) return CLD_EINVAL;
+  if ((flags & ~(CLD_FLAG_HTML | kUtf8Flags | kPublicFlags)) != 0 || !utf8_flags_ok(flags)) return CLD_EINVAL;
   if (int rc = check_batch(buf, offsets, n, out)) return rc;
   if (doc_flags && !doc_flags_ok(doc_flags, n)) return CLD_EINVAL;
   if (n == 0) return CLD_OK;
-  if ((flags & CLD_FLAG_CHECK_UTF8) && !docs_fit_int32(offsets, n)) return CLD_EINVAL;
+  if ((flags & kUtf8Flags) && !docs_fit_int32(offsets, n)) return CLD_EINVAL;
   int rc = cld_init(nullptr, 0);
   if (rc) return rc;
   std::shared_lock<std::shared_mutex> tl(g_swap_mu);
-  const uint32_t cf = flags & (kCldFlags | CLD_FLAG_CHECK_UTF8);
+  const uint32_t cf = flags & (kCldFlags | kUtf8Flags);
   std::vector<uint8_t> special;
   std::vector<uint32_t> priors;
   bool html = false, routed = false;           // some document is HTML; some routing byte is set
   if ((rc = apply_hints(buf, offsets, n, hints, (flags & CLD_FLAG_HTML) != 0, doc_flags, &special, &priors, &html,
-                        &routed)))
+                        &routed, (flags & CLD_FLAG_SCRUB_UTF8) != 0)))
     return rc;
   const Batch b{buf, offsets, n, out, cf, (routed || !priors.empty()) ? special.data() : nullptr,
                 priors.empty() ? nullptr : priors.data(), html, vp};
@@ -2419,6 +2476,7 @@ int cld_detect_batch_ex(const uint8_t* buf, const uint64_t* offsets, size_t n, c
 // ExtDetectLanguageSummaryCheckUTF8 (compact_lang_det.cc:317-355) over a batch.
 int cld_detect_batch_checked(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
                              uint32_t flags, cld_result* out, int32_t* valid_prefix) {
+  // (CLD_FLAG_SCRUB_UTF8 falls to the mask: this entry rejects, that flag repairs)
   if ((flags & ~(CLD_FLAG_HTML | CLD_FLAG_CHECK_UTF8 | kPublicFlags)) != 0 || (n > 0 && !valid_prefix)) return CLD_EINVAL;
   return detect_batch_ex(buf, offsets, n, hints, flags | CLD_FLAG_CHECK_UTF8, out, valid_prefix);
 }
@@ -2480,6 +2538,61 @@ int cld_valid_prefix_batch(const uint8_t* buf, const uint64_t* offsets, size_t n
   return CLD_OK;
 }
 
+int32_t cld_scrub_utf8_host(const uint8_t* doc, size_t len, uint8_t* out) {
+  if (len > 0x7FFFFFFFull || (len > 0 && (!doc || !out))) return CLD_EINVAL;
+  return (int32_t)scrub_host(doc, len, out, nullptr);
+}
+
+int cld_scrub_utf8_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n, uint8_t* d_out,
+                          int32_t* d_replaced, void* stream) {
+  if (n > 0x7FFFFFFFu || (n > 0 && (!d_buf || !d_offsets || !d_out))) return CLD_EINVAL;
+  int rc = cld_init(nullptr, 0);
+  if (rc) return rc;
+  if (device < 0 || device >= (int)g_devs.size()) return CLD_EINVAL;
+  if (n == 0) return CLD_OK;
+  Device* d = g_devs[device];
+  HIP_OK(hipSetDevice(d->id));
+  // (no scratch of the context is used: nothing to serialise with other batches)
+  HIP_OK(cld_launch_scrub(d_buf, d_offsets, (int)n, d_out, d_replaced, nullptr, 0,
+                          stream ? (hipStream_t)stream : d->stream));
+  return CLD_OK;
+}
+
+int cld_scrub_utf8_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, uint8_t* out_buf, int32_t* replaced) {
+  if (n > 0 && (!buf || !offsets || !out_buf)) return CLD_EINVAL;
+  if (n == 0) return CLD_OK;
+  if (n > 0x7FFFFFFFu || !offsets_nondecreasing(offsets, n) || !docs_fit_int32(offsets, n)) return CLD_EINVAL;
+  int rc = cld_init(nullptr, 0);
+  if (rc) return rc;
+  Device* d = g_devs[0];
+  std::lock_guard<std::mutex> lk(d->mu);
+  HIP_OK(hipSetDevice(d->id));
+  HIP_OK(hipStreamWaitEvent(d->stream, d->done, 0));   // an earlier batch may still use d_cbuf / d_vp
+  // pieces of at most 256 MB of text / 4M documents (one document at least), as cld_valid_prefix_batch
+  constexpr uint64_t kPieceBytes = 256ull << 20;
+  constexpr size_t kPieceDocs = 4u << 20;
+  for (size_t a = 0; a < n;) {
+    size_t m = 1;
+    while (a + m < n && m < kPieceDocs && offsets[a + m + 1] - offsets[a] <= kPieceBytes) ++m;
+    const uint64_t base = offsets[a], bytes = offsets[a + m] - base;
+    if (d->d_buf.reserve(std::max<size_t>(bytes, 1)) || d->d_cbuf.reserve(std::max<size_t>(bytes, 1)) ||
+        d->d_offs.reserve(m + 1) || d->d_vp.reserve(m))
+      return CLD_ENOMEM;
+    if (bytes) HIP_OK(hipMemcpyAsync(d->d_buf, buf + base, bytes, hipMemcpyHostToDevice, d->stream));
+    HIP_OK(hipMemcpyAsync(d->d_offs, offsets + a, (m + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, d->stream));
+    // (the offsets go up as the caller wrote them: both buffer bases are biased instead; d_vp holds the counts)
+    uint8_t* cb = d->d_cbuf;
+    int32_t* cnt = replaced ? (int32_t*)d->d_vp : nullptr;
+    HIP_OK(cld_launch_scrub(d->d_buf - base, d->d_offs, (int)m, cb - base, cnt, nullptr, bytes, d->stream));
+    // out_buf is indexed like the input from its first document on: out_buf[offsets[i] - offsets[0] + j]
+    if (bytes) HIP_OK(hipMemcpyAsync(out_buf + (base - offsets[0]), cb, bytes, hipMemcpyDeviceToHost, d->stream));
+    if (cnt) HIP_OK(hipMemcpyAsync(replaced + a, cnt, m * sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
+    HIP_OK(hipStreamSynchronize(d->stream));
+    a += m;
+  }
+  return CLD_OK;
+}
+
 int cld_detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
                          uint32_t flags, cld_result* out, cld_chunk* chunks, size_t chunk_cap,
                          uint64_t* chunk_offsets) {
@@ -2488,8 +2601,8 @@ int cld_detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t n, 
 
 int cld_detect_batch_docflags(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
                               const uint32_t* doc_flags, uint32_t flags, cld_result* out, int32_t* valid_prefix) {
-  if (valid_prefix && !(flags & CLD_FLAG_CHECK_UTF8)) return CLD_EINVAL;
-  if (!doc_flags)
+  if (valid_prefix && !(flags & kUtf8Flags)) return CLD_EINVAL;
+  if (!doc_flags && !(valid_prefix && (flags & CLD_FLAG_SCRUB_UTF8)))
     return valid_prefix ? cld_detect_batch_checked(buf, offsets, n, hints, flags, out, valid_prefix)
                         : cld_detect_batch_ex(buf, offsets, n, hints, flags, out);
   return detect_batch_ex(buf, offsets, n, hints, flags, out, valid_prefix, doc_flags);
@@ -2507,13 +2620,14 @@ int cld_detect_batch_vec_docflags(const uint8_t* buf, const uint64_t* offsets, s
 static int detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
                             const uint32_t* doc_flags, uint32_t flags, cld_result* out, cld_chunk* chunks,
                             size_t chunk_cap, uint64_t* chunk_offsets) {
-  if ((flags & ~(CLD_FLAG_HTML | CLD_FLAG_CHECK_UTF8 | kPublicFlags)) != 0 || !chunk_offsets || (chunk_cap > 0 && !chunks))
+  if ((flags & ~(CLD_FLAG_HTML | kUtf8Flags | kPublicFlags)) != 0 || !utf8_flags_ok(flags) || !chunk_offsets ||
+      (chunk_cap > 0 && !chunks))
     return CLD_EINVAL;
   if (int rc = check_batch(buf, offsets, n, out)) return rc;
   if (doc_flags && !doc_flags_ok(doc_flags, n)) return CLD_EINVAL;
   chunk_offsets[0] = 0;
   if (n == 0) return CLD_OK;
-  if ((flags & CLD_FLAG_CHECK_UTF8) && !docs_fit_int32(offsets, n)) return CLD_EINVAL;
+  if ((flags & kUtf8Flags) && !docs_fit_int32(offsets, n)) return CLD_EINVAL;
   int rc = cld_init(nullptr, 0);
   if (rc) return rc;
   std::shared_lock<std::shared_mutex> tl(g_swap_mu);
@@ -2521,9 +2635,9 @@ static int detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t 
   std::vector<uint32_t> priors;
   bool html = false, routed = false;
   if ((rc = apply_hints(buf, offsets, n, hints, (flags & CLD_FLAG_HTML) != 0, doc_flags, &special, &priors, &html,
-                        &routed)))
+                        &routed, (flags & CLD_FLAG_SCRUB_UTF8) != 0)))
     return rc;
-  const Batch b{buf, offsets, n, out, flags & (kCldFlags | CLD_FLAG_CHECK_UTF8),
+  const Batch b{buf, offsets, n, out, flags & (kCldFlags | kUtf8Flags),
                 (routed || !priors.empty()) ? special.data() : nullptr, priors.empty() ? nullptr : priors.data(), html};
   const size_t ndev = g_devs.size();
   std::vector<std::vector<cld_chunk>> vs(ndev);
@@ -2561,7 +2675,7 @@ int cld_detect_batch_device(int device, const uint8_t* d_buf, const uint64_t* d_
 
 int cld_detect_batch_device_ex(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
                                uint64_t buf_bytes, cld_result* d_out, uint32_t flags, void* stream) {
-  if ((flags & ~(kPrepFlags | kPublicFlags)) != 0) return CLD_EINVAL;
+  if ((flags & ~(kPrepFlags | kPublicFlags)) != 0 || !utf8_flags_ok(flags)) return CLD_EINVAL;
   int rc = cld_init(nullptr, 0);
   if (rc) return rc;
   if (device < 0 || device >= (int)g_devs.size() || n > 0x7FFFFFFFu) return CLD_EINVAL;
@@ -2663,9 +2777,9 @@ static int detect_batch_device_vec(int device, const uint8_t* d_buf, const uint6
                                    int big_regions, cld_result* d_out, cld_chunk* d_chunks, uint64_t chunk_cap,
                                    uint64_t* d_chunk_offsets, int32_t* d_valid_prefix, cld_vec_status* d_status,
                                    void* stream) {
-  const bool chk = (flags & CLD_FLAG_CHECK_UTF8) != 0;
-  if ((flags & ~(CLD_FLAG_HTML | CLD_FLAG_CHECK_UTF8 | kPublicFlags)) != 0 || n > 0x7FFFFFFFu ||
-      (d_valid_prefix && !chk) || (chunk_cap > 0 && !d_chunks) || (hint_text_bytes && !d_hint_text) ||
+  const bool chk = (flags & CLD_FLAG_CHECK_UTF8) != 0, scrub = (flags & CLD_FLAG_SCRUB_UTF8) != 0;
+  if ((flags & ~(CLD_FLAG_HTML | kUtf8Flags | kPublicFlags)) != 0 || (chk && scrub) || n > 0x7FFFFFFFu ||
+      (d_valid_prefix && !chk && !scrub) || (chunk_cap > 0 && !d_chunks) || (hint_text_bytes && !d_hint_text) ||
       (n > 0 && (!d_buf || !d_offsets || !d_out || !d_chunk_offsets || !d_status)))
     return CLD_EINVAL;
   int rc = cld_init(nullptr, 0);
@@ -2706,17 +2820,30 @@ static int detect_batch_device_vec(int device, const uint8_t* d_buf, const uint6
   HIP_OK(hipMemsetAsync(d_status, 0, sizeof(cld_vec_status), s));
   HIP_OK(hipMemsetAsync(d->d_counters, 0, kCtrSlots * sizeof(uint32_t), s));
   // CLD_FLAG_CHECK_UTF8: the kernels get the prepared batch, in which a rejected
-  // document is empty; the hints, the regions and the results go by the documents as given
+  // document is empty; the hints, the regions and the results go by the documents as given.
+  // CLD_FLAG_SCRUB_UTF8: the kernels and the hints' lang= scan get the scrubbed copy, which has the
+  // offsets as given; the prefixes (the context's own where the caller wants none) count the repaired
+  // documents for the status
   const uint8_t* kb = d_buf;
   const uint64_t* ko = d_offsets;
+  const int32_t* vps = nullptr;
   if (chk) {
     if ((rc = enqueue_prepare(d, d_buf, d_offsets, n, buf_bytes, CLD_FLAG_CHECK_UTF8, s, d_valid_prefix))) return rc;
     kb = d->p_buf;
     ko = d->p_offs;
+    vps = d->chk_vp;
+  } else if (scrub) {
+    if (!d_valid_prefix) {
+      if (d->d_vp.reserve(n)) return CLD_ENOMEM;
+      d_valid_prefix = d->d_vp;
+    }
+    if ((rc = enqueue_prepare(d, d_buf, d_offsets, n, buf_bytes, CLD_FLAG_SCRUB_UTF8, s, d_valid_prefix))) return rc;
+    kb = d->p_buf;
+    vps = d_valid_prefix;
   }
   if (hinted)
-    HIP_OK(cld_launch_apply_hints(&d->H, d_buf, d_offsets, (int)n, d_hints, d_hint_text, hint_text_bytes, plain,
-                                  d_doc_flags, nullptr, V.pri, V.sp, s));
+    HIP_OK(cld_launch_apply_hints(&d->H, scrub ? kb : d_buf, d_offsets, (int)n, d_hints, d_hint_text, hint_text_bytes,
+                                  plain, d_doc_flags, nullptr, V.pri, V.sp, s));
   uint64_t* scan = (uint64_t*)(uint8_t*)d->d_sscr;
   HIP_OK(cld_launch_vec_plan(d_offsets, (int)n, mode, scan, s));
   HIP_OK(cld_launch_scan_lengths((int)n, V.pool_off, scan, s));
@@ -2736,7 +2863,7 @@ static int detect_batch_device_vec(int device, const uint8_t* d_buf, const uint6
                              hinted ? (const uint32_t*)V.pri : nullptr, hb, hf, hpz, hgz, V.pool, V.pool_off, V.nch,
                              s));
   if (chk && (rc = enqueue_fixup(d, d_out, n, s, V.nch))) return rc;
-  HIP_OK(cld_launch_vec_finish(d_offsets, (int)n, V.nch, chk ? d->chk_vp : nullptr, d_out,
+  HIP_OK(cld_launch_vec_finish(d_offsets, (int)n, V.nch, vps, d_out,
                                g_tab.meta.unknown_language, scan, d_status, s));
   HIP_OK(cld_launch_scan_lengths((int)n, d_chunk_offsets, scan, s));
   HIP_OK(cld_launch_vec_gather_chunks(V.pool, V.pool_off, d_chunk_offsets, (int)n, d_chunks, chunk_cap, d_status, s));
@@ -2970,6 +3097,21 @@ const char* detect_language_checked(const char* text, int* valid_prefix_bytes) {
   if (valid_prefix_bytes) *valid_prefix_bytes = vp;
   if (vp < 0 || (size_t)vp < len) return cld_language_code(26);   // UNKNOWN_LANGUAGE, not mapped to English there
   return detect_language(t);
+}
+
+// The repair in place of the rejection: scrub(text) in a private copy (the
+// caller's text is never written), then detect_language on it.
+const char* detect_language_scrubbed(const char* text, int* replaced_bytes) {
+  const char* t = text ? text : "";
+  const size_t len = strlen(t);
+  if (len > 0x7FFFFFFFull) {                    // (positions and counts are int, as in the checked entry)
+    if (replaced_bytes) *replaced_bytes = CLD_EINVAL;
+    return cld_language_code(26);
+  }
+  std::string copy(t, len);
+  const size_t r = scrub_host((const uint8_t*)t, len, (uint8_t*)&copy[0], nullptr);
+  if (replaced_bytes) *replaced_bytes = (int)r;
+  return detect_language(r ? copy.c_str() : t);
 }
 
 }  // extern "C"

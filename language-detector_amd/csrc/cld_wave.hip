@@ -358,6 +358,40 @@ __device__ bool load_document(const DevTables& T, const uint8_t* __restrict__ g,
   return true;
 }
 
+// A rewritten HTML page (cld_html.hip) in which dropped '&'s (hflag bit 1 on the
+// byte after them) stand between a single letter B of another script and a
+// letter C.  The reference's letters loop lets B through when the next byte is
+// Common, and a raw '&' is; it then meets the undecodable '&' with B's script
+// still in hand, and C's script decides whether the span breaks at the '&'
+// (getonescriptspan.cc:876-931): "AB&C" can be two spans where the rewritten
+// "ABC" is one.  B is a single letter of another script iff the letter A in
+// front of it has a different one (A's is the span's, or Inherited), so the
+// test needs no span: such a page is left to k_long, whose span builder hands
+// it to the sequential span source.  Run once per page after load_document;
+// plain documents (hf == nullptr) never get here.
+template <int CAP>
+__device__ bool stale_script_amp(const DevTables& T, Smem<CAP>& s, int L, const uint8_t* __restrict__ hf, int lane) {
+  const int common = (int)T.common, inherited = (int)T.inherited;
+  int hit = 0;
+  for (int x = lane; x < L; x += 64) {
+    if (!((s.ent[x >> 6] >> (x & 63)) & 1) || !(gld(hf + x) & 2) || (s.doc[x] & 0xC0) == 0x80) continue;
+    const int sc = s.sn[x];
+    if (sc == 0 || sc == common) continue;             // C is no letter: the run ends there either way
+    int b = x - 1;
+    while (b > 0 && (s.doc[b] & 0xC0) == 0x80) --b;
+    if (b < 0) continue;
+    const int scb = s.sn[b];
+    if (scb == 0 || scb == common || scb == inherited) continue;
+    int a = b - 1;
+    while (a > 0 && (s.doc[a] & 0xC0) == 0x80) --a;
+    if (a < 0) continue;                               // B starts the page: its script is the span's
+    const int sca = s.sn[a];
+    if (sca == 0 || sca == common) continue;           // B starts a run: likewise
+    hit |= (sca == inherited || (scb != sca && sc != sca)) ? 1 : 0;
+  }
+  return __ballot(hit != 0) != 0;
+}
+
 // ------------------------------------------------ stage 1: one script span
 // GetOneScriptSpan (getonescriptspan.cc:799-1027, plain text) as runs:
 // ' ' + run1 + ' ' + run2 + ' ' ... + runK + ' ' + "   \0".  A run starts at
@@ -1602,6 +1636,7 @@ __device__ bool detect(const DevTables& T, const uint8_t* __restrict__ g, int L,
   }
   bool lowv;
   if (!load_document<CAP>(T, g, L, s, lane, hf, lowv)) return false;
+  if (hf && stale_script_amp<CAP>(T, s, L, hf, lane)) return false;   // (uniform)
   mark(0);
   if (lane == 0) s.dt.init();
   if (lane < 8) s.ring[lane >> 2][lane & 3] = 0;
