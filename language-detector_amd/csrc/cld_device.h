@@ -21,6 +21,11 @@ struct DevTbl {
   const uint64_t* adds;       // per indirect entry: its langprob's three tote adds (lng::tote_adds),
                               // bit 63 set if the langprob is non-zero (k_long; built on device)
   uint32_t size_one, size, key_mask, n_ind, n_buckets;
+  // derived where the struct is filled (parse_tbl): size - 1 and ~key_mask.
+  // k_wave reads them as kernel arguments where it probes, one scalar load
+  // each, instead of computing them per document and carrying them (spilled)
+  // across its span loop
+  uint32_t size_m1, nkey_mask;
 };
 
 // Everything DetectLanguageSummaryV2 reads, as device pointers into one

@@ -50,7 +50,11 @@ __global__ __launch_bounds__(256) void k_vec_gather(const cld_chunk* __restrict_
 #ifndef WAVE_WPS
 #define WAVE_WPS 8
 #endif
-template <int CAP, int WPB>
+// PLAIN: the instantiation for a batch with no routing bytes, priors, HTML
+// rewrite or stage profile (the five nullable pointers below all null): they
+// are compile-time null there, so the per-document, per-span and per-chunk
+// tests on them and the registers that carry them are gone.
+template <int CAP, int WPB, bool PLAIN>
 __global__ __launch_bounds__(64 * WPB, WAVE_WPS) void k_wave(DevTables T, const uint8_t* __restrict__ buf,
                                                    const uint64_t* __restrict__ offs, int n,
                                                    cld_result* __restrict__ out,
@@ -64,8 +68,9 @@ __global__ __launch_bounds__(64 * WPB, WAVE_WPS) void k_wave(DevTables T, const 
   __shared__ wave::Smem<CAP> smem[WPB];
   // wave index through readfirstlane: the document pointer, its length, the
   // result pointer and the LDS base are then scalars, not VGPRs live across
-  // the whole document
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  // the whole document.  One wave per workgroup: smem[0], whose field
+  // addresses are compile-time constants
+  const int wv = WPB == 1 ? 0 : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   // XCD-aware: workgroups go round-robin over the 8 XCDs, so block b's
   // documents come from slice b & 7 of the batch.  Neighbouring documents
   // then share an XCD (and its L2) for the lines they share.
@@ -75,7 +80,7 @@ __global__ __launch_bounds__(64 * WPB, WAVE_WPS) void k_wave(DevTables T, const 
   // k_route has already listed the HTML documents (for k_long) and those
   // longer than CAP (for k_long); hinted plain ones are scored here with their
   // ApplyHints priors
-  const uint8_t sp = special ? special[i] : (uint8_t)0;
+  const uint8_t sp = (!PLAIN && special) ? special[i] : (uint8_t)0;
   if (sp & kSpecialHtml) return;
   const uint32_t* pri = (sp & kSpecialPriors) ? priors + 16ull * i : nullptr;
   const uint64_t a = offs[i], b = offs[i + 1];
@@ -88,8 +93,9 @@ __global__ __launch_bounds__(64 * WPB, WAVE_WPS) void k_wave(DevTables T, const 
   // the document's own ScoreAsQuads / BestEffort ride in its routing byte (i is
   // wave-uniform, so this stays scalar)
   const uint32_t dcf = cflags | cld_special_cflags(sp);
-  const bool rq = !wave::detect<CAP>(T, (rw ? hbuf : buf) + a, (int)len, smem[wv], lane, &out[i],
-                                     (i & 63) == 0 ? prof : nullptr, dcf, pri, rw ? hflag + a : nullptr);
+  const bool rq = !wave::detect<CAP, PLAIN>(T, (rw ? hbuf : buf) + a, (int)len, smem[wv], lane, &out[i],
+                                            (!PLAIN && (i & 63) == 0) ? prof : nullptr, dcf, pri,
+                                            rw ? hflag + a : nullptr);
   if (rq && lane == 0) {                       // rare (state-machine or capacity cases)
     if (requeue_list) {
       uint32_t k = atomicAdd(&counters[kCtrRequeue], 1u);
@@ -919,8 +925,14 @@ hipError_t cld_launch_wave(const DevTables* T, const uint8_t* buf, const uint64_
                      requeue_list, special_list, special_ctr, hist2);
   const int per = ((n + kWaveWPB - 1) / kWaveWPB + 7) / 8;   // k_wave's XCD slices
   dim3 grid(8 * per), block(64 * kWaveWPB);
-  hipLaunchKernelGGL((cld::k_wave<kWaveCap, kWaveWPB>), grid, block, 0, s, *T, buf, offs, n, out,
-                     requeue_list, counters, prof, special, special_list, special_ctr, cflags, priors, hbuf, hflag);
+  // a plain batch (no routing bytes, priors, rewritten pages or stage profile)
+  // takes the instantiation without them
+  if (!special && !priors && !hbuf && !hflag && !prof)
+    hipLaunchKernelGGL((cld::k_wave<kWaveCap, kWaveWPB, true>), grid, block, 0, s, *T, buf, offs, n, out,
+                       requeue_list, counters, prof, special, special_list, special_ctr, cflags, priors, hbuf, hflag);
+  else
+    hipLaunchKernelGGL((cld::k_wave<kWaveCap, kWaveWPB, false>), grid, block, 0, s, *T, buf, offs, n, out,
+                       requeue_list, counters, prof, special, special_list, special_ctr, cflags, priors, hbuf, hflag);
   return hipGetLastError();
 }
 
@@ -928,7 +940,7 @@ hipError_t cld_launch_wave_only(const DevTables* T, const uint8_t* buf, const ui
                                 uint32_t* requeue_list, uint32_t* counters, uint32_t cflags, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   const int per = ((n + kWaveWPB - 1) / kWaveWPB + 7) / 8;
-  hipLaunchKernelGGL((cld::k_wave<kWaveCap, kWaveWPB>), dim3(8 * per), dim3(64 * kWaveWPB), 0, s, *T, buf, offs, n,
+  hipLaunchKernelGGL((cld::k_wave<kWaveCap, kWaveWPB, true>), dim3(8 * per), dim3(64 * kWaveWPB), 0, s, *T, buf, offs, n,
                      out, requeue_list, counters, nullptr, nullptr, nullptr, 0, cflags, nullptr, nullptr, nullptr);
   return hipGetLastError();
 }

@@ -88,6 +88,21 @@ __device__ __forceinline__ uint4 gld4(const uint32_t* p) {      // one 16-byte l
 }
 
 // ---------------------------------------------------------- state machines
+// A wave-uniform value through an empty asm with a scalar-register constraint:
+// what is derived from it is computed where this stands (see PIN below).
+__device__ __forceinline__ uint32_t in_sgpr(uint32_t v) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
+// A state machine whose scalars are pinned where this stands (k_wave's CJK and
+// fall-back branches: their strides and bounds are then made inside the
+// branch, not per document).
+__device__ __forceinline__ DevSM pinned_sm(const DevSM& sm) {
+  DevSM p = sm;
+  p.state0 = in_sgpr(p.state0); p.state0_size = in_sgpr(p.state0_size); p.total = in_sgpr(p.total);
+  p.shift = in_sgpr(p.shift);
+  return p;
+}
 __device__ __forceinline__ uint32_t sm16(const DevSM& sm, int64_t i) {
   return (i < 0 || i >= (int64_t)sm.total) ? 0u : (uint32_t)gld(sm.t16 + i);
 }
@@ -126,8 +141,7 @@ __device__ __forceinline__ int script_num(const DevTables& T, const Src& s, int 
 
 // UTF8GenericPropertyBigOneByte on the CJK unigram machine, srclen =
 // kAdvanceOneChar[lead] (cldutil.cc:221-226, utf8statetable.cc:271-320)
-__device__ int uni_prop(const DevTables& T, const uint8_t* s, int srclen) {
-  const DevSM& sm = T.uni;
+__device__ int uni_prop_sm(const DevSM& sm, const uint8_t* s, int srclen) {
   int64_t b0 = sm.state0;
   int sh = (int)sm.shift;
   uint8_t c = s[0];
@@ -153,6 +167,9 @@ __device__ int uni_prop(const DevTables& T, const uint8_t* s, int srclen) {
     e = 0;
   }
   return (uint8_t)e;
+}
+__device__ __forceinline__ int uni_prop(const DevTables& T, const uint8_t* s, int srclen) {
+  return uni_prop_sm(T.uni, s, srclen);
 }
 
 __device__ __forceinline__ bool in_state_zero(const DevSM& sm, int64_t tb) {
@@ -435,8 +452,14 @@ __device__ __forceinline__ uint64_t pair_hash(uint64_t a, uint64_t b) {   // cld
 
 // QuadHashV3Lookup4 / OctaHashV3Lookup4 cldutil_shared.h:380-454: one 16-byte
 // bucket gather, first of four slots whose masked key matches.
+// PIN (k_wave, here and in the probes below): a table scalar passes through an
+// empty asm with a scalar-register constraint where it is used, so what is
+// derived from it (a "has buckets" predicate, a size mask) is made there, from
+// one scalar load of the kernel arguments, instead of once per document and
+// carried -- spilled -- across the span loop.
+template <bool PIN = false>
 __device__ __forceinline__ uint32_t lookup4(const DevTbl& t, uint32_t sub, uint32_t key) {
-  if (t.n_buckets == 0) return 0;
+  if ((PIN ? in_sgpr(t.n_buckets) : t.n_buckets) == 0) return 0;
   const uint4 b = gld4(t.b + 4 * (size_t)sub);
   if (((key ^ b.x) & t.key_mask) == 0) return b.x;
   if (((key ^ b.y) & t.key_mask) == 0) return b.y;
@@ -444,8 +467,9 @@ __device__ __forceinline__ uint32_t lookup4(const DevTbl& t, uint32_t sub, uint3
   if (((key ^ b.w) & t.key_mask) == 0) return b.w;
   return 0;
 }
+template <bool PIN = false>
 __device__ __forceinline__ uint32_t quad_lookup(const DevTbl& t, uint32_t h) {
-  return lookup4(t, (h + (h >> 12)) & (t.size - 1), h & t.key_mask);
+  return lookup4<PIN>(t, (h + (h >> 12)) & (PIN ? in_sgpr(t.size_m1) : t.size - 1), h & t.key_mask);
 }
 // GetQuadHits' probe (cldutil.cc:356-363): QuadHashV3Lookup4 on the first
 // quadgram table, then on the second one only on a miss.  Both buckets are
@@ -453,20 +477,19 @@ __device__ __forceinline__ uint32_t quad_lookup(const DevTbl& t, uint32_t h) {
 // so a miss costs one L2 round trip, not two.  ind: the indirect subscript,
 // bit 31 set for the second table.  Returns the matching keyvalue or 0.
 //
-// PIN (k_wave, which runs at 64 VGPRs): the two table sizes pass through an
-// empty asm with a scalar-register constraint where they are used, so the
-// size masks are computed there on the scalar unit.  Left to itself the
-// compiler computes quad2's once per document on the VALU (for the carry) and
-// keeps it in a vector register across the span loop -- a scratch spill there.
-__device__ __forceinline__ uint32_t in_sgpr(uint32_t v) {
-  asm volatile("" : "+s"(v));
-  return v;
-}
+// PIN (k_wave, which runs at 64 VGPRs): the two size masks (DevTbl::size_m1)
+// and the bucket counts are pinned where they are used.  Left to itself the
+// compiler computes quad2's mask once per document on the VALU (for the
+// carry) and keeps it in a vector register across the span loop -- a scratch
+// spill there.
 template <bool PIN = false>
 __device__ __forceinline__ uint32_t quad_probe(const DevTbl& q1, const DevTbl& q2, uint32_t h, uint32_t& ind) {
-  const bool two = q2.size != 0 && q2.n_buckets != 0;
-  const uint32_t m1 = (PIN ? in_sgpr(q1.size) : q1.size) - 1, m2 = (PIN ? in_sgpr(q2.size) : q2.size) - 1;
-  const uint4 b1 = q1.n_buckets ? gld4(q1.b + 4 * (size_t)((h + (h >> 12)) & m1)) : make_uint4(0, 0, 0, 0);
+  const uint32_t nb1 = PIN ? in_sgpr(q1.n_buckets) : q1.n_buckets, nb2 = PIN ? in_sgpr(q2.n_buckets) : q2.n_buckets;
+  const uint32_t sz2 = PIN ? in_sgpr(q2.size) : q2.size;
+  const bool two = sz2 != 0 && nb2 != 0;
+  const uint32_t m1 = PIN ? in_sgpr(q1.size_m1) : q1.size - 1, m2 = PIN ? in_sgpr(q2.size_m1) : q2.size - 1;
+  const uint32_t nk1 = PIN ? q1.nkey_mask : ~q1.key_mask, nk2 = PIN ? q2.nkey_mask : ~q2.key_mask;
+  const uint4 b1 = nb1 ? gld4(q1.b + 4 * (size_t)((h + (h >> 12)) & m1)) : make_uint4(0, 0, 0, 0);
   const uint4 b2 = two ? gld4(q2.b + 4 * (size_t)((h + (h >> 12)) & m2)) : make_uint4(0, 0, 0, 0);
   auto match = [](uint4 b, uint32_t key, uint32_t mask) -> uint32_t {
     if (((key ^ b.x) & mask) == 0) return b.x;
@@ -475,24 +498,25 @@ __device__ __forceinline__ uint32_t quad_probe(const DevTbl& q1, const DevTbl& q
     if (((key ^ b.w) & mask) == 0) return b.w;
     return 0u;
   };
-  uint32_t probs = q1.n_buckets ? match(b1, h & q1.key_mask, q1.key_mask) : 0u;
+  uint32_t probs = nb1 ? match(b1, h & q1.key_mask, q1.key_mask) : 0u;
   ind = 0;
-  if (probs == 0 && q2.size != 0) {
+  if (probs == 0 && sz2 != 0) {
     probs = two ? match(b2, h & q2.key_mask, q2.key_mask) : 0u;
-    if (probs) ind = (probs & ~q2.key_mask) | 0x80000000u;
+    if (probs) ind = (probs & nk2) | 0x80000000u;
   } else if (probs) {
-    ind = probs & ~q1.key_mask;
+    ind = probs & nk1;
   }
   return probs;
 }
 // NARROW (k_wave): the bucket subscript in 32 bits -- the table size is a u32,
 // so only the low word of h + (h >> 12) takes part, the same subscript -- and
-// the size mask stays a scalar operand instead of a 64-bit vector value.
+// the size mask stays a scalar operand instead of a 64-bit vector value; the
+// table scalars are pinned (PIN above).
 template <bool NARROW = false>
 __device__ __forceinline__ uint32_t octa_lookup(const DevTbl& t, uint64_t h) {
-  const uint32_t sub = NARROW ? ((uint32_t)h + (uint32_t)(h >> 12)) & (t.size - 1)
+  const uint32_t sub = NARROW ? ((uint32_t)h + (uint32_t)(h >> 12)) & in_sgpr(t.size_m1)
                               : (uint32_t)((h + (h >> 12)) & (uint64_t)(t.size - 1));
-  return lookup4(t, sub, (uint32_t)(h >> 4) & t.key_mask);
+  return lookup4<NARROW>(t, sub, (uint32_t)(h >> 4) & t.key_mask);
 }
 __device__ __forceinline__ uint32_t ind_at(const DevTbl& t, uint32_t i) { return i < t.n_ind ? gld(t.ind + i) : 0u; }
 

@@ -197,6 +197,7 @@ bool parse_tbl(const std::vector<uint8_t>& b, uint32_t id, DevTbl* t) {
   const cldt_table_header* h = (const cldt_table_header*)p;
   t->size_one = h->size_one; t->size = h->size; t->key_mask = h->key_mask;
   t->n_ind = h->n_ind; t->n_buckets = h->n_buckets_stored;
+  t->size_m1 = h->size - 1; t->nkey_mask = ~h->key_mask;
   uint64_t bo = off + sizeof(cldt_table_header);
   t->b = at<const uint32_t*>(bo);
   t->ind = at<const uint32_t*>(bo + 16ull * h->n_buckets_stored);
@@ -204,6 +205,7 @@ bool parse_tbl(const std::vector<uint8_t>& b, uint32_t id, DevTbl* t) {
   // subscript is masked with size-1, so every such bucket must be stored; the
   // indirect reads are bounded by n_ind on the device
   return (bo % 16) == 0 && (h->size == 0 || (h->size & (h->size - 1)) == 0) &&
+         t->size_m1 == t->size - 1 && t->nkey_mask == ~t->key_mask &&   // (the derived fields k_wave probes with)
          h->size <= h->n_buckets_stored &&
          sizeof(cldt_table_header) + 16ull * h->n_buckets_stored + 4ull * h->n_ind <= size;
 }

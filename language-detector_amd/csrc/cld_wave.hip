@@ -242,9 +242,13 @@ __device__ __forceinline__ uint32_t pack_lowered(uint64_t e) {
 // sequential scanner: the document tiles into lead+continuation characters
 // and a scan started at any character either stops on it or continues to the
 // scan result of the next character.
-template <int CAP>
+// PLAIN (here and in the stages below): k_wave's plain instantiation -- no
+// rewritten HTML (hf null, s.ent neither written nor read), no priors, no
+// stage profile, all at compile time.
+template <int CAP, bool PLAIN>
 __device__ bool load_document(const DevTables& T, const uint8_t* __restrict__ g, int L, Smem<CAP>& s, int lane,
                               const uint8_t* __restrict__ hf, bool& lowv) {
+  if constexpr (PLAIN) hf = nullptr;
   lowv = false;                          // s.a.low holds every character's pack_lowered (the fast path)
   using C = Cfg<CAP>;
   static_assert(CAP == 256 && C::DOC == 288, "one aligned dword per lane covers the document");
@@ -270,7 +274,7 @@ __device__ bool load_document(const DevTables& T, const uint8_t* __restrict__ g,
         const uint64_t m = __ballot(w * 64 + lane < L && gld(hf + w * 64 + lane) != 0);
         if (lane == 0) s.ent[w] = m;
       }
-    } else if (lane < C::NM) {
+    } else if (!PLAIN && lane < C::NM) {
       s.ent[lane] = 0ull;
     }
   }
@@ -399,7 +403,7 @@ __device__ bool stale_script_amp(const DevTables& T, Smem<CAP>& s, int L, const 
 // character the letters loop would break on; the gap after it is skipped to
 // the next letter stop, which either continues the span or starts the next.
 // Returns text_bytes (0 = no further span); *next advances like next_byte_.
-template <int CAP>
+template <int CAP, bool PLAIN>
 __device__ int next_span(const DevTables& T, Smem<CAP>& s, int L, int& next, int& ulscript, int lane) {
   lane = lane_here();
   using C = Cfg<CAP>;
@@ -431,7 +435,7 @@ __device__ int next_span(const DevTables& T, Smem<CAP>& s, int L, int& next, int
         } else {
           // (a lookahead onto a rewritten HTML entity sees the raw '&': script 0)
           const int xn = x + utf8_len((uint8_t)c);
-          const int sc2 = (xn < 64 * C::NM && ((s.ent[xn >> 6] >> (xn & 63)) & 1)) ? 0 : s.sn[xn];
+          const int sc2 = (!PLAIN && xn < 64 * C::NM && ((s.ent[xn >> 6] >> (xn & 63)) & 1)) ? 0 : s.sn[xn];
           brk = sc2 != common && sc2 != spanscript;
         }
       }
@@ -479,7 +483,13 @@ __device__ int next_span(const DevTables& T, Smem<CAP>& s, int L, int& next, int
 __device__ __forceinline__ void setb(uint64_t& o, int i, uint32_t v) {
   o = (o & ~(0xFFull << (8 * i))) | ((uint64_t)(v & 0xFF) << (8 * i));
 }
-__device__ bool lower_char_sm(const DevSM& sm, const uint8_t* src, int n, uint64_t& out, int& olen) {
+// PIN (k_wave's fall-back lowercaser): the machine's scalars are pinned here
+// (pinned_sm), so the strides and bounds derived from them are made in this
+// branch and not per document.
+template <bool PIN = false>
+__device__ bool lower_char_sm(const DevSM& sm_in, const uint8_t* src, int n, uint64_t& out, int& olen) {
+  const DevSM sm_pin = PIN ? pinned_sm(sm_in) : DevSM{};
+  const DevSM& sm = PIN ? sm_pin : sm_in;
   const int sh = (int)sm.shift;
   const int nE = 1 << sh;
   const int64_t tb0 = sm.state0;
@@ -587,7 +597,7 @@ __device__ int lower_span(const DevTables& T, Smem<CAP>& s, int text_bytes, int 
       if ((e >> 10) & 1) {
         olen = (int)((e >> 11) & 15);
         o = e >> 32;
-      } else if (!lower_char(T, &s.sbuf[p], n, o, olen)) {
+      } else if (!lower_char_sm<true>(T.lower, &s.sbuf[p], n, o, olen)) {
         bad = 1;
         olen = 0;
       }
@@ -616,7 +626,7 @@ __device__ int lower_span(const DevTables& T, Smem<CAP>& s, int text_bytes, int 
 // lower in this form (bit 10 clear, 4 output bytes, or not a well-formed 1-3
 // byte sequence) is redone by next_span + lower_span, unchanged.
 // Returns the lowered text_bytes, 0 = no further span, -1 = re-queue.
-template <int CAP>
+template <int CAP, bool PLAIN>
 __device__ int span_lowered(const DevTables& T, Smem<CAP>& s, int L, int& next, int& ulscript, int lane, bool lowv) {
   lane = lane_here();
   using C = Cfg<CAP>;
@@ -669,7 +679,7 @@ __device__ int span_lowered(const DevTables& T, Smem<CAP>& s, int L, int& next, 
         } else {
           // (a lookahead onto a rewritten HTML entity sees the raw '&': script 0)
           const int xn = x + utf8_len((uint8_t)c);
-          const int sc2 = (xn < 64 * C::NM && ((s.ent[xn >> 6] >> (xn & 63)) & 1)) ? 0 : s.sn[xn];
+          const int sc2 = (!PLAIN && xn < 64 * C::NM && ((s.ent[xn >> 6] >> (xn & 63)) & 1)) ? 0 : s.sn[xn];
           brk = sc2 != common && sc2 != spanscript;
         }
       }
@@ -710,7 +720,7 @@ __device__ int span_lowered(const DevTables& T, Smem<CAP>& s, int L, int& next, 
     e0 = e1; e1 = e2; e2 = e3;
   }
   if (__ballot(bad != 0)) {
-    const int tb = next_span<CAP>(T, s, L, next, ulscript, lane);
+    const int tb = next_span<CAP, PLAIN>(T, s, L, next, ulscript, lane);
     return lower_span<CAP>(T, s, tb, lane);
   }
   if (run) {                                         // the document ended inside a run
@@ -1023,9 +1033,9 @@ __device__ bool octa_hits(const DevTables& T, Smem<CAP>& s, int start, int nw, i
     const int tx = __popcll(mp) + __popcll(mx), td = __popcll(md);
     if (xb + tx > C::NX || db + td > C::ND) { over = true; break; }
     int o = ox;
-    if (pp) { s.x_off[o] = (uint16_t)pws[r]; s.x_ind[o] = pp & ~T.distinctocta.key_mask; ++o; }
-    if (xp) { s.x_off[o] = (uint16_t)ws[r]; s.x_ind[o] = xp & ~T.distinctocta.key_mask; }
-    if (dp) { s.d_off[od] = (uint16_t)ws[r]; s.d_ind[od] = dp & ~T.deltaocta.key_mask; }
+    if (pp) { s.x_off[o] = (uint16_t)pws[r]; s.x_ind[o] = pp & T.distinctocta.nkey_mask; ++o; }
+    if (xp) { s.x_off[o] = (uint16_t)ws[r]; s.x_ind[o] = xp & T.distinctocta.nkey_mask; }
+    if (dp) { s.d_off[od] = (uint16_t)ws[r]; s.d_ind[od] = dp & T.deltaocta.nkey_mask; }
     xb += tx; db += td;
   }
   if (over) return false;
@@ -1044,13 +1054,14 @@ __device__ int cjk_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, in
   if (text[start] == ' ') ++start;
   int b = 0;
   eb = 0;
+  const DevSM uni = pinned_sm(T.uni);     // (its strides and bounds: made here, in the CJK branch)
   uint32_t endmax = (uint32_t)start;
   for (int w0 = start; w0 < limit; w0 += 64) {
     const int p = w0 + lane;
     int prop = 0, len = 0;
     if (p < limit && (text[p] & 0xC0) != 0x80) {
       len = utf8_len(text[p]);
-      prop = uni_prop(T, text + p, len);
+      prop = uni_prop_sm(uni, text + p, len);
       endmax = (uint32_t)(p + len) > endmax ? (uint32_t)(p + len) : endmax;
     }
     // the unigram's langprobs straight to the base emissions, as quad_hits' hits
@@ -1069,18 +1080,18 @@ __device__ int cjk_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, in
       const int len2 = utf8_len(text[p + len]) + len;
       if (6 <= len2) {
         const uint32_t bh = bi_hash_v2(text + p, len2);
-        dp = quad_lookup(T.deltabi, bh);
-        xp = quad_lookup(T.distinctbi, bh);
+        dp = quad_lookup<true>(T.deltabi, bh);
+        xp = quad_lookup<true>(T.distinctbi, bh);
       }
     }
     const uint64_t md = __ballot(dp != 0), mx = __ballot(xp != 0);
     if (dp) {
       int k = dcount + below(md);
-      if (k < C::ND) { s.d_off[k] = (uint16_t)p; s.d_ind[k] = dp & ~T.deltabi.key_mask; }
+      if (k < C::ND) { s.d_off[k] = (uint16_t)p; s.d_ind[k] = dp & T.deltabi.nkey_mask; }
     }
     if (xp) {
       int k = xcount + below(mx);
-      if (k < C::NX) { s.x_off[k] = (uint16_t)p; s.x_ind[k] = xp & ~T.distinctbi.key_mask; }
+      if (k < C::NX) { s.x_off[k] = (uint16_t)p; s.x_ind[k] = xp & T.distinctbi.nkey_mask; }
     }
     dcount += __popcll(md); xcount += __popcll(mx);
   }
@@ -1127,9 +1138,10 @@ __device__ __forceinline__ void dt_add_wave(DocTote& dt, int k, int bytes, int s
 // without materialising linear[]: every emitted langprob gets its chunk from
 // rank arithmetic.  Linear order is the seed, then (offset, delta < distinct <
 // base, index); chunk k closes after base-type emission E_k.
-template <int CAP>
+template <int CAP, bool PLAIN>
 __device__ bool score_round(const DevTables& T, Smem<CAP>& s, int ulscript, bool cjk, int nb, int eb, int nd, int nx,
                             int dummy_off, int& ring_sel, int lane, const uint32_t* __restrict__ pri) {
+  if constexpr (PLAIN) pri = nullptr;
   lane = lane_here();
   using C = Cfg<CAP>;
   const DevTbl& dob = cjk ? T.deltabi : T.deltaocta;
@@ -1608,13 +1620,15 @@ __device__ __forceinline__ int finish_document(const DevTables& T, DocTote& dt, 
 }
 
 // ------------------------------------------------------ the document
-template <int CAP>
+template <int CAP, bool PLAIN>
 __device__ bool detect(const DevTables& T, const uint8_t* __restrict__ g, int L, Smem<CAP>& s, int lane,
                        cld_result* __restrict__ out, unsigned long long* __restrict__ prof, uint32_t cflags,
                        const uint32_t* __restrict__ pri, const uint8_t* __restrict__ hf) {
+  if constexpr (PLAIN) { prof = nullptr; pri = nullptr; hf = nullptr; }
   // optional per-stage cycle accounting (CLD_PROFILE_STAGES=1): 0 load, 1 span
   // + lower (2 stays 0 since they are one pass), 3 quad/uni, 4 octa/bi,
-  // 5 score, 6 document level
+  // 5 score, 6 document level.  It measures the general instantiation (the
+  // plain one has no profile pointer).
   long long t_stage = prof ? (long long)clock64() : 0;
   auto mark = [&](int st) {
     if (prof) {
@@ -1635,7 +1649,7 @@ __device__ bool detect(const DevTables& T, const uint8_t* __restrict__ g, int L,
     return true;
   }
   bool lowv;
-  if (!load_document<CAP>(T, g, L, s, lane, hf, lowv)) return false;
+  if (!load_document<CAP, PLAIN>(T, g, L, s, lane, hf, lowv)) return false;
   if (hf && stale_script_amp<CAP>(T, s, L, hf, lane)) return false;   // (uniform)
   mark(0);
   if (lane == 0) s.dt.init();
@@ -1644,12 +1658,13 @@ __device__ bool detect(const DevTables& T, const uint8_t* __restrict__ g, int L,
   int next = 0, total = 0;
   for (;;) {
     int ulscript = 0;
-    const int tb = span_lowered<CAP>(T, s, L, next, ulscript, lane, lowv);
+    const int tb = span_lowered<CAP, PLAIN>(T, s, L, next, ulscript, lane, lowv);
     mark(1);
     if (tb == 0) break;
     if (tb < 0) return false;
     int rt = rtype_of(T, ulscript);
-    if ((cflags & kCLDFlagScoreAsQuads) && rt != RTypeCJK) rt = RTypeMany;   // scoreonescriptspan.cc:1318-1320
+    // (pinned: the flag test is made here, not kept as a mask across the loop)
+    if ((in_sgpr(cflags) & kCLDFlagScoreAsQuads) && rt != RTypeCJK) rt = RTypeMany;   // scoreonescriptspan.cc:1318-1320
     if (rt == RTypeNone || rt == RTypeOne) {
       if (lane == 0) s.dt.add((uint16_t)default_language(T, ulscript), tb, tb, 100);
       wsync();
@@ -1671,7 +1686,7 @@ __device__ bool detect(const DevTables& T, const uint8_t* __restrict__ g, int L,
       }
       if (endo < tb) return false;     // a second round would be needed (never for short documents)
       int rsel;
-      if (1 < tb && !score_round<CAP>(T, s, ulscript, cjk, nb, eb, nd, nx, endo, rsel, lane, pri)) return false;
+      if (1 < tb && !score_round<CAP, PLAIN>(T, s, ulscript, cjk, nb, eb, nd, nx, endo, rsel, lane, pri)) return false;
       mark(5);
     }
     total += tb;

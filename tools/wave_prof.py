@@ -18,6 +18,8 @@ def main():
     os.environ.setdefault("CLD_PROFILE_STAGES", "1")
     cld_amd.init_device(0)
     cfgs = [a.split(":") for a in sys.argv[1:]] or [("c2", 1_000_000), ("c4", 200_000), ("c5", 200_000), ("c3", 20000)]
+    print("(the wave cycles are those of k_wave's general instantiation: with a stage profile the plain one, "
+          "which an unprofiled plain batch runs, is not launched)")
     for cfg, n in cfgs:
         n = int(n)
         buf, offs = corpus.GENERATORS[cfg](n)
