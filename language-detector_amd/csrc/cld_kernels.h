@@ -14,6 +14,24 @@ constexpr int kWaveCap = 256;
 constexpr int kWaveWPB = WAVE_WPB;   // waves (documents) per workgroup
 // Largest kLgProbV2Tbl score byte the packed wave tote accepts (runtime checks the blob)
 constexpr int kMaxLgProbScore = 16;
+// k_wave's deferred tail (plain batches): the wave leaves each document a slot
+// of 16-byte words in a record buffer and k_wtail (cld_wtail.hip), one lane
+// per document, makes the chunk summaries, the DocTote and the document level.
+//   word 0, the header, written by the wave for every document of the batch:
+//     x = records that follow, or kTailNone (k_wtail leaves the document alone:
+//         skipped or re-queued by the wave, or empty and already written)
+//     y = total text bytes
+//   words 1..x, in DocTote::Add order:
+//     a scored chunk     x = key1 | key2 << 8 (per-script numbers, 0xFF: none)
+//                        y = score1 | score2 << 16
+//                        z = lo | hi << 16 (the chunk's offsets as SetChunkSummary reads them)
+//                        w = grams | ulscript << 16
+//     an unscored span   x = kTailSpan, y = language, z = text bytes
+//                        (RTypeNone / RTypeOne: Add(language, bytes, bytes, 100))
+// A document with more than kTailRecs records is re-queued by the wave.
+constexpr int kTailRecs = 31;
+constexpr size_t kTailSlotBytes = 16 * (1 + kTailRecs);
+constexpr uint32_t kTailNone = 0xFFFFFFFFu, kTailSpan = 0x10000u;
 
 
 // Device counter slots (three 64-byte lines, zeroed per batch)
@@ -105,11 +123,15 @@ hipError_t cld_launch_vec_gather_chunks(const cld_chunk* pool, const uint64_t* p
 // CLD_FLAG_BEST_EFFORT (compact_lang_det.h:343, :349), the same for every document;
 // a document whose routing byte carries kSpecialQuads / kSpecialBestEffort is
 // scored with cflags | cld_special_cflags(special[i]).
+// tail_recs (nullable; n * kTailSlotBytes, 16-byte aligned, not zeroed): a plain
+// batch -- special, priors, hbuf, hflag and prof all null -- runs k_wave's
+// deferred instantiation and then k_wtail over it; null keeps the tail in the
+// wave, as every other batch does.
 hipError_t cld_launch_wave(const DevTables* T, const uint8_t* buf, const uint64_t* offs, int n,
                            cld_result* out, uint32_t* requeue_list, uint32_t* counters,
                            unsigned long long* prof, const uint8_t* special, uint32_t* special_list,
                            int special_ctr, uint32_t cflags, const uint32_t* priors, const uint8_t* hbuf,
-                           const uint8_t* hflag, uint32_t* hist2, hipStream_t s);
+                           const uint8_t* hflag, uint32_t* hist2, uint8_t* tail_recs, hipStream_t s);
 // k_wave alone, without k_route: the caller guarantees every document is at
 // most kWaveCap bytes (run_tiny's request-sized batches).  Documents the wave
 // kernel cannot finish are listed under counters[kCtrRequeue], or, with

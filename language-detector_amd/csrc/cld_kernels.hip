@@ -1,6 +1,8 @@
 // cld_kernels.hip -- batch kernels over the device pipeline.
 //
 //  k_wave<CAP>   one wavefront per document of <= CAP bytes, state in LDS.
+//  k_wtail       one lane per document: the summaries and document level of
+//                the documents k_wave's deferred instantiation left records for.
 //  k_long        one wavefront per document of any length up to lng::kDocCap,
 //                per-wave slot in HBM; persistent grid over the wave kernel's
 //                re-queue list.
@@ -54,7 +56,12 @@ __global__ __launch_bounds__(256) void k_vec_gather(const cld_chunk* __restrict_
 // rewrite or stage profile (the five nullable pointers below all null): they
 // are compile-time null there, so the per-document, per-span and per-chunk
 // tests on them and the registers that carry them are gone.
-template <int CAP, int WPB, bool PLAIN>
+// DEFER (with PLAIN; cld_launch_wave's plain batches): the wave stops where a
+// span's chunks have their top two keys and writes them as records into
+// document i's slot of `recs` (kTailSlotBytes each, layout in cld_kernels.h);
+// k_wtail below finishes the documents, 64 to a wave.  Every document i < n
+// gets a header, so k_wtail never reads a slot nobody wrote.
+template <int CAP, int WPB, bool PLAIN, bool DEFER = false>
 __global__ __launch_bounds__(64 * WPB, WAVE_WPS) void k_wave(DevTables T, const uint8_t* __restrict__ buf,
                                                    const uint64_t* __restrict__ offs, int n,
                                                    cld_result* __restrict__ out,
@@ -64,7 +71,8 @@ __global__ __launch_bounds__(64 * WPB, WAVE_WPS) void k_wave(DevTables T, const 
                                                    const uint8_t* __restrict__ special,
                                                    uint32_t* __restrict__ special_list, int special_ctr,
                                                    uint32_t cflags, const uint32_t* __restrict__ priors,
-                                                   const uint8_t* __restrict__ hbuf, const uint8_t* __restrict__ hflag) {
+                                                   const uint8_t* __restrict__ hbuf, const uint8_t* __restrict__ hflag,
+                                                   uint4* __restrict__ recs) {
   __shared__ wave::Smem<CAP> smem[WPB];
   // wave index through readfirstlane: the document pointer, its length, the
   // result pointer and the LDS base are then scalars, not VGPRs live across
@@ -85,7 +93,11 @@ __global__ __launch_bounds__(64 * WPB, WAVE_WPS) void k_wave(DevTables T, const 
   const uint32_t* pri = (sp & kSpecialPriors) ? priors + 16ull * i : nullptr;
   const uint64_t a = offs[i], b = offs[i + 1];
   const int64_t len = (int64_t)(b - a);
-  if (len > CAP) return;
+  uint4* const rec = DEFER ? recs + (size_t)i * (kTailSlotBytes / 16) : nullptr;
+  if (len > CAP) {
+    if (DEFER && lane == 0) rec[0] = make_uint4(kTailNone, 0u, 0u, 0u);
+    return;
+  }
   // stage cycles (CLD_PROFILE_STAGES=1) are sampled on one document in 64, so
   // the accounting atomics do not themselves become the bottleneck
   // a rewritten HTML page (cld_html.hip) is read from hbuf, with its lookahead marks
@@ -93,9 +105,11 @@ __global__ __launch_bounds__(64 * WPB, WAVE_WPS) void k_wave(DevTables T, const 
   // the document's own ScoreAsQuads / BestEffort ride in its routing byte (i is
   // wave-uniform, so this stays scalar)
   const uint32_t dcf = cflags | cld_special_cflags(sp);
-  const bool rq = !wave::detect<CAP, PLAIN>(T, (rw ? hbuf : buf) + a, (int)len, smem[wv], lane, &out[i],
-                                            (!PLAIN && (i & 63) == 0) ? prof : nullptr, dcf, pri,
-                                            rw ? hflag + a : nullptr);
+  const bool rq = !wave::detect<CAP, PLAIN, DEFER>(T, (rw ? hbuf : buf) + a, (int)len, smem[wv], lane, &out[i],
+                                                   (!PLAIN && (i & 63) == 0) ? prof : nullptr, dcf, pri,
+                                                   rw ? hflag + a : nullptr, rec);
+  // (an empty document has its result already; a re-queued one gets it from k_long)
+  if (DEFER && lane == 0 && (rq || len == 0)) rec[0] = make_uint4(kTailNone, 0u, 0u, 0u);
   if (rq && lane == 0) {                       // rare (state-machine or capacity cases)
     if (requeue_list) {
       uint32_t k = atomicAdd(&counters[kCtrRequeue], 1u);
@@ -120,6 +134,10 @@ __device__ __forceinline__ void wave_append(bool pred, uint32_t* ctr, uint32_t* 
   base = (uint32_t)__shfl((int)base, leader, 64);
   if (pred) list[base + __popcll(m & wave::lanemask_lt(lane))] = val;
 }
+
+}  // namespace cld
+#include "cld_wtail.hip"
+namespace cld {
 
 __global__ __launch_bounds__(256) void k_route_vec(int n, uint32_t* __restrict__ counters,
                                                   uint32_t* __restrict__ long_list) {
@@ -919,20 +937,32 @@ hipError_t cld_launch_wave(const DevTables* T, const uint8_t* buf, const uint64_
                            cld_result* out, uint32_t* requeue_list, uint32_t* counters,
                            unsigned long long* prof, const uint8_t* special, uint32_t* special_list,
                            int special_ctr, uint32_t cflags, const uint32_t* priors, const uint8_t* hbuf,
-                           const uint8_t* hflag, uint32_t* hist2, hipStream_t s) {
+                           const uint8_t* hflag, uint32_t* hist2, uint8_t* tail_recs, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(cld::k_route, dim3((n + 255) / 256), dim3(256), 0, s, offs, n, special, kWaveCap, counters,
                      requeue_list, special_list, special_ctr, hist2);
   const int per = ((n + kWaveWPB - 1) / kWaveWPB + 7) / 8;   // k_wave's XCD slices
   dim3 grid(8 * per), block(64 * kWaveWPB);
   // a plain batch (no routing bytes, priors, rewritten pages or stage profile)
-  // takes the instantiation without them
-  if (!special && !priors && !hbuf && !hflag && !prof)
+  // takes the instantiation without them; with a record buffer its tail is
+  // deferred to k_wtail, 64 documents to a wave
+  const bool plain = !special && !priors && !hbuf && !hflag && !prof;
+  if (plain && tail_recs) {
+    uint4* recs = reinterpret_cast<uint4*>(tail_recs);
+    hipLaunchKernelGGL((cld::k_wave<kWaveCap, kWaveWPB, true, true>), grid, block, 0, s, *T, buf, offs, n, out,
+                       requeue_list, counters, prof, special, special_list, special_ctr, cflags, priors, hbuf, hflag,
+                       recs);
+    hipLaunchKernelGGL(cld::k_wtail, dim3((n + 63) / 64), dim3(64), 0, s, *T, n, recs, out, requeue_list, counters,
+                       cflags);
+  } else if (plain) {
     hipLaunchKernelGGL((cld::k_wave<kWaveCap, kWaveWPB, true>), grid, block, 0, s, *T, buf, offs, n, out,
-                       requeue_list, counters, prof, special, special_list, special_ctr, cflags, priors, hbuf, hflag);
-  else
+                       requeue_list, counters, prof, special, special_list, special_ctr, cflags, priors, hbuf, hflag,
+                       nullptr);
+  } else {
     hipLaunchKernelGGL((cld::k_wave<kWaveCap, kWaveWPB, false>), grid, block, 0, s, *T, buf, offs, n, out,
-                       requeue_list, counters, prof, special, special_list, special_ctr, cflags, priors, hbuf, hflag);
+                       requeue_list, counters, prof, special, special_list, special_ctr, cflags, priors, hbuf, hflag,
+                       nullptr);
+  }
   return hipGetLastError();
 }
 
@@ -941,7 +971,7 @@ hipError_t cld_launch_wave_only(const DevTables* T, const uint8_t* buf, const ui
   if (n <= 0) return hipSuccess;
   const int per = ((n + kWaveWPB - 1) / kWaveWPB + 7) / 8;
   hipLaunchKernelGGL((cld::k_wave<kWaveCap, kWaveWPB, true>), dim3(8 * per), dim3(64 * kWaveWPB), 0, s, *T, buf, offs, n,
-                     out, requeue_list, counters, nullptr, nullptr, nullptr, 0, cflags, nullptr, nullptr, nullptr);
+                     out, requeue_list, counters, nullptr, nullptr, nullptr, 0, cflags, nullptr, nullptr, nullptr, nullptr);
   return hipGetLastError();
 }
 

@@ -506,6 +506,11 @@ struct Device {
   bool diagnostics() const { return fused_diagnostics() || fault_doc != 0xFFFFFFFFu; }
   DevBuf<uint32_t> d_counters;
   DevBuf<uint32_t> d_requeue;
+  // k_wave's deferred tail (plain batches): kTailSlotBytes per document, written by
+  // k_wave and read by k_wtail inside one enqueue().  Scratch like d_requeue:
+  // batches of a context are serialised on `done`, the host path's chunks too.
+  bool wave_tail = true;        // CLD_WAVE_TAIL=0: plain batches keep the tail in the wave
+  DevBuf<uint8_t> d_wrec;
   DevBuf<uint8_t> d_buf;        // cld_prepare_batch / cld_valid_prefix_batch: the uploaded batch
   DevBuf<uint64_t> d_offs;
   DevBuf<uint8_t> d_sbuf;       // prepared text (CLD_FLAG_STRIP_EXTRAS / CSTRING)
@@ -739,6 +744,7 @@ int init_device(Device* d) {
   ALLOC_OK(d->d_counters, kCtrSlots);
   ALLOC_OK(d->d_lhist, 256);
   d->long_order = env_long("CLD_LONG_ORDER", 1) != 0;
+  d->wave_tail = env_long("CLD_WAVE_TAIL", 1) != 0;
   hipDeviceProp_t prop;
   HIP_OK(hipGetDeviceProperties(&prop, d->id));
   if (env_long("CLD_PROFILE_STAGES", 0) > 0) {
@@ -930,6 +936,13 @@ int enqueue(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, cld_r
   const size_t n1 = std::max<size_t>(n, 1);
   if (d->d_requeue.reserve(n1) || d->d_requeue2.reserve(n1)) return CLD_ENOMEM;
   if (d->n_slots > 0 && d->long_order && (d->d_lsorted.reserve(n1) || d->d_lkey.reserve(n1))) return CLD_ENOMEM;
+  // a plain batch (cld_launch_wave's test) defers k_wave's tail to k_wtail
+  // (512 B per document; without room for the records the batch keeps the tail in the wave)
+  bool tail = d->wave_tail && !special && !priors && !hbuf && !d->d_prof;
+  if (tail && d->d_wrec.reserve(n1 * kTailSlotBytes) != CLD_OK) {
+    (void)hipGetLastError();   // (the failed hipMalloc's error must not surface at the next launch check)
+    tail = false;
+  }
   if (d->ev_used == d->ev_pool.size()) {
     hipEvent_t t[4]{};
     for (auto& e : t) HIP_OK(hipEventCreate(&e));
@@ -954,7 +967,8 @@ int enqueue(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, cld_r
   // HTML pages the rewrite did not take join k_long's list (its sequential
   // span source scans them in HTML mode, cld_seq.hip)
   HIP_OK(cld_launch_wave(&d->T, buf, offs, (int)n, out, d->d_requeue, ctr, d->d_prof, special, d->d_requeue,
-                         kCtrRequeue, cflags, priors, hbuf, hflag, d->long_order ? d->d_lhist : nullptr, s));
+                         kCtrRequeue, cflags, priors, hbuf, hflag, d->long_order ? d->d_lhist : nullptr,
+                         tail ? (uint8_t*)d->d_wrec : nullptr, s));
   HIP_OK(hipEventRecord(ev[1], s));
   {
     const uint32_t* list = d->d_requeue;

@@ -313,6 +313,9 @@ __device__ bool load_document(const DevTables& T, const uint8_t* __restrict__ g,
     for (int w = 0; w < C::NM; ++w) ev[w] = idx[w] >= 0 ? gld(T.cpt + idx[w]) : 0ull;
 #pragma unroll
     for (int w = 0; w < C::NM; ++w) {
+      // (uniform) no window past the document: nothing reads s.sn, s.lsm or the
+      // values of s.a.low there (the span loops stop at L, the lookaheads at L + 3)
+      if (w * 64 >= L) break;
       // script number at every byte (0 off the lead bytes: only lead bytes are read)
       const int p = w * 64 + lane;
       const uint64_t e = ev[w];
@@ -1133,14 +1136,31 @@ __device__ __forceinline__ void dt_add_wave(DocTote& dt, int k, int bytes, int s
   wsync();
 }
 
+// The records k_wave's deferred instantiation leaves for k_wtail (layout in
+// cld_kernels.h).  Scores stay below 65536 (Cfg's tote headroom), offsets below
+// Cfg::LB, keys are bytes (-1, no key, travels as 0xFF: SetChunkSummary indexes
+// the key table with (uint8_t)key).
+__device__ __forceinline__ uint4 tail_chunk_record(int k1, int k2, int s1, int s2, int grams, int lo, int hi, int ulscript) {
+  return make_uint4((uint32_t)(uint8_t)k1 | (uint32_t)(uint8_t)k2 << 8, (uint32_t)s1 | (uint32_t)s2 << 16,
+                    (uint32_t)lo | (uint32_t)hi << 16, (uint32_t)grams | (uint32_t)ulscript << 16);
+}
+__device__ __forceinline__ uint4 tail_span_record(int lang, int bytes) {
+  return make_uint4(kTailSpan, (uint32_t)lang, (uint32_t)bytes, 0u);
+}
+
 // ------------------------------------- stage 4: linearize + chunk + score
 // LinearizeAll/ChunkAll/ScoreAllHits (scoreonescriptspan.cc:856-1031, 208-302)
 // without materialising linear[]: every emitted langprob gets its chunk from
 // rank arithmetic.  Linear order is the seed, then (offset, delta < distinct <
 // base, index); chunk k closes after base-type emission E_k.
-template <int CAP, bool PLAIN>
+// DEFER (k_wave's deferred instantiation): the span's chunks leave as records
+// in the document's slot `rec` (TailSlot, cld_kernels.h), nrec of them written
+// so far; k_wtail makes their summaries and the DocTote adds, one lane per
+// document.  False also when the slot has no room for them.
+template <int CAP, bool PLAIN, bool DEFER = false>
 __device__ bool score_round(const DevTables& T, Smem<CAP>& s, int ulscript, bool cjk, int nb, int eb, int nd, int nx,
-                            int dummy_off, int& ring_sel, int lane, const uint32_t* __restrict__ pri) {
+                            int dummy_off, int& ring_sel, int lane, const uint32_t* __restrict__ pri,
+                            uint4* __restrict__ rec, int& nrec) {
   if constexpr (PLAIN) pri = nullptr;
   lane = lane_here();
   using C = Cfg<CAP>;
@@ -1348,6 +1368,20 @@ __device__ bool score_round(const DevTables& T, Smem<CAP>& s, int ulscript, bool
     }
     wsync();
   }
+  const int nsum = K < kMaxSummaries ? K : kMaxSummaries;
+  if constexpr (DEFER) {
+    // one record per chunk, lane k's: the keys, scores and gram count as they
+    // stand, the chunk's byte range as SetChunkSummary reads it
+    if (nrec + nsum > kTailRecs) return false;           // (uniform) no room in the slot: handed on
+    if (lane < nsum) {
+      const uint32_t lo_k = s.lo[lane];
+      const int lo = lo_k == 0xFFFFFFFFu ? dummy_off : (int)lo_k;
+      int hi = dummy_off;
+      if (lane + 1 < K && s.lo[lane + 1] != 0xFFFFFFFFu) hi = (int)s.lo[lane + 1];
+      rec[1 + nrec + lane] = tail_chunk_record(ck1, ck2, cs1, cs2, cgr, lo, hi, ulscript);
+    }
+    nrec += nsum;
+  } else {
   // SetChunkSummary (scoreonescriptspan.cc:60-96) for every chunk at once, one
   // lane per chunk; the DocTote adds then run in chunk order on lane 0
   int sum_lang = 0, sum_bytes = 0, sum_rel = 0;
@@ -1375,10 +1409,10 @@ __device__ bool score_round(const DevTables& T, Smem<CAP>& s, int ulscript, bool
     sum_lang = (uint16_t)lang1; sum_bytes = bytes; sum_rel = rd < rsc ? rd : rsc;
     cs1 = s1;
   }
-  const int nsum = K < kMaxSummaries ? K : kMaxSummaries;
   for (int k = 0; k < nsum; ++k) {
     const int l1 = rdl(sum_lang, k), by = rdl(sum_bytes, k), sc = rdl(cs1, k), rl = rdl(sum_rel, k);
     dt_add_wave(s.dt, l1, by, sc, rl, lane);
+  }
   }
   // the ring keeps the last four distinct langprobs
   if (lane == 0) {
@@ -1620,11 +1654,18 @@ __device__ __forceinline__ int finish_document(const DevTables& T, DocTote& dt, 
 }
 
 // ------------------------------------------------------ the document
-template <int CAP, bool PLAIN>
+// DEFER: no DocTote and no document level here.  The document's slot `rec`
+// gets one record per chunk and per unscored span in order, then its header
+// (count, total); k_wtail finishes it.  A document that returns false, or an
+// empty one (its result is written here), leaves its header to the caller.
+template <int CAP, bool PLAIN, bool DEFER = false>
 __device__ bool detect(const DevTables& T, const uint8_t* __restrict__ g, int L, Smem<CAP>& s, int lane,
                        cld_result* __restrict__ out, unsigned long long* __restrict__ prof, uint32_t cflags,
-                       const uint32_t* __restrict__ pri, const uint8_t* __restrict__ hf) {
+                       const uint32_t* __restrict__ pri, const uint8_t* __restrict__ hf,
+                       uint4* __restrict__ rec = nullptr) {
+  static_assert(PLAIN || !DEFER, "only the plain instantiation defers its tail");
   if constexpr (PLAIN) { prof = nullptr; pri = nullptr; hf = nullptr; }
+  int nrec = 0;
   // optional per-stage cycle accounting (CLD_PROFILE_STAGES=1): 0 load, 1 span
   // + lower (2 stays 0 since they are one pass), 3 quad/uni, 4 octa/bi,
   // 5 score, 6 document level.  It measures the general instantiation (the
@@ -1652,7 +1693,7 @@ __device__ bool detect(const DevTables& T, const uint8_t* __restrict__ g, int L,
   if (!load_document<CAP, PLAIN>(T, g, L, s, lane, hf, lowv)) return false;
   if (hf && stale_script_amp<CAP>(T, s, L, hf, lane)) return false;   // (uniform)
   mark(0);
-  if (lane == 0) s.dt.init();
+  if (!DEFER && lane == 0) s.dt.init();
   if (lane < 8) s.ring[lane >> 2][lane & 3] = 0;
   wsync();
   int next = 0, total = 0;
@@ -1666,8 +1707,14 @@ __device__ bool detect(const DevTables& T, const uint8_t* __restrict__ g, int L,
     // (pinned: the flag test is made here, not kept as a mask across the loop)
     if ((in_sgpr(cflags) & kCLDFlagScoreAsQuads) && rt != RTypeCJK) rt = RTypeMany;   // scoreonescriptspan.cc:1318-1320
     if (rt == RTypeNone || rt == RTypeOne) {
-      if (lane == 0) s.dt.add((uint16_t)default_language(T, ulscript), tb, tb, 100);
-      wsync();
+      if constexpr (DEFER) {
+        if (nrec + 1 > kTailRecs) return false;          // (uniform) no room in the slot: handed on
+        if (lane == 0) rec[1 + nrec] = tail_span_record(default_language(T, ulscript), tb);
+        ++nrec;
+      } else {
+        if (lane == 0) s.dt.add((uint16_t)default_language(T, ulscript), tb, tb, 100);
+        wsync();
+      }
     } else {
       const bool cjk = rt == RTypeCJK;
       lowv = false;                      // the hit stages and scoring reuse s.a
@@ -1686,14 +1733,21 @@ __device__ bool detect(const DevTables& T, const uint8_t* __restrict__ g, int L,
       }
       if (endo < tb) return false;     // a second round would be needed (never for short documents)
       int rsel;
-      if (1 < tb && !score_round<CAP, PLAIN>(T, s, ulscript, cjk, nb, eb, nd, nx, endo, rsel, lane, pri)) return false;
+      if (1 < tb &&
+          !score_round<CAP, PLAIN, DEFER>(T, s, ulscript, cjk, nb, eb, nd, nx, endo, rsel, lane, pri, rec, nrec))
+        return false;
       mark(5);
     }
     total += tb;
   }
-  const int ok = finish_document<true>(T, s.dt, total, false, out, lane, (cflags & kCLDFlagBestEffort) != 0);
-  mark(6);
-  return ok != 0;
+  if constexpr (DEFER) {
+    if (lane == 0) rec[0] = make_uint4((uint32_t)nrec, (uint32_t)total, 0u, 0u);
+    return true;
+  } else {
+    const int ok = finish_document<true>(T, s.dt, total, false, out, lane, (cflags & kCLDFlagBestEffort) != 0);
+    mark(6);
+    return ok != 0;
+  }
 }
 
 }  // namespace wave
