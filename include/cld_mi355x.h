@@ -316,6 +316,76 @@ int cld_scrub_utf8_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, 
 int cld_scrub_utf8_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n, uint8_t* d_out,
                           int32_t* d_replaced, void* stream);
 
+/* A batch of results grouped by language, and the chosen documents packed into
+ * a new batch: what a caller does with the results of a crawl shard, without
+ * leaving the GPU (the reference service counts its answers per language,
+ * handlers.go:163 incLanguageCount).
+ *
+ * The key of a document is summary_lang, or lang3[0] with CLD_GROUP_TOP1;
+ * with CLD_GROUP_RELIABLE_ONLY a document with is_reliable == 0 gets the key
+ * UNKNOWN_LANGUAGE (26).  Its bin is min(key, CLD_NUM_LANGUAGES): bin 614
+ * collects every key that is no Language value, CLD_LANG_FAILED among them.
+ * Any other bit in group_flags: CLD_EINVAL.
+ *   counts[CLD_GROUP_BINS]             documents per bin
+ *   bin_bytes[CLD_GROUP_BINS]          (NULL: not wanted; needs offsets, else
+ *                                      CLD_EINVAL) the sum of offsets[i + 1] -
+ *                                      offsets[i] over each bin's documents
+ *   order[n]                           (NULL: not wanted) the document indices
+ *                                      sorted by (bin, index): a stable sort
+ *   group_offsets[CLD_GROUP_BINS + 1]  (NULL: not wanted) the exclusive prefix
+ *                                      sum of counts, group_offsets[615] == n:
+ *                                      bin b's documents are order[group_offsets[b]
+ *                                      .. group_offsets[b + 1]), ascending
+ *   cld_group_by_language         the host reference, no GPU.
+ *   cld_group_by_language_device  every pointer in device memory of GPU
+ *                                 `device` (8-byte aligned where it holds 64-bit
+ *                                 words or results), enqueued on `stream` (NULL:
+ *                                 the runtime's); asynchronous, waits for nothing
+ *                                 on the host, uses none of the context's scratch
+ *                                 and may run from several threads at once, each
+ *                                 with a workspace of its own: d_work holds
+ *                                 work_bytes >= cld_group_work_bytes(n) bytes
+ *                                 (a smaller one: CLD_ENOSPC, nothing enqueued)
+ *                                 and is free again when the call's work on the
+ *                                 stream is done.  d_results is only read.
+ *                                 order is the same
+ *                                 from run to run: no atomic decides a position.
+ *   cld_gather_docs_device        documents d_index[0..m) of the batch (d_buf,
+ *                                 d_offsets[0..n_src]) packed back to back:
+ *                                 d_out_offsets[0..m] = the exclusive prefix sum
+ *                                 of their lengths, always the true totals, and
+ *                                 d_out_buf[0, min(d_out_offsets[m], out_cap))
+ *                                 their bytes; nothing at or past d_out_buf +
+ *                                 out_cap is written (out_cap == 0, d_out_buf
+ *                                 NULL: the sizing pass).  An index may repeat;
+ *                                 an index >= n_src is an empty document.  The
+ *                                 output is a batch for every cld_detect_batch_device*
+ *                                 entry, with buf_bytes = d_out_offsets[m].
+ *                                 d_out_buf and d_buf must not overlap.  The
+ *                                 usual d_index is a slice of d_order: d_order +
+ *                                 group_offsets[L], m = counts[L], and bin_bytes[L]
+ *                                 sizes d_out_buf exactly.  Workspace and stream
+ *                                 as above, cld_group_work_bytes(m).
+ * cld_group_work_bytes does not grow past a few MB: both entries cut their
+ * work into a fixed number of workgroup ranges.  n or m (or n_src) above
+ * INT32_MAX: CLD_EINVAL.  n == 0 / m == 0: CLD_OK, with zero counts, byte
+ * totals and group offsets, and d_out_offsets[0] = 0, written where those
+ * pointers are not NULL. */
+#define CLD_NUM_LANGUAGES 614u      /* Language enum values 0..613 (generated_language.h) */
+#define CLD_GROUP_BINS    615u      /* bin 614: every key >= 614, CLD_LANG_FAILED (0xFFFF) among them */
+#define CLD_GROUP_TOP1          1u  /* key = lang3[0]; default: summary_lang */
+#define CLD_GROUP_RELIABLE_ONLY 2u  /* is_reliable == 0  ->  key UNKNOWN_LANGUAGE (26) */
+size_t cld_group_work_bytes(size_t n);
+int cld_group_by_language(const cld_result* results, size_t n, uint32_t group_flags, const uint64_t* offsets,
+                          uint64_t* counts, uint64_t* bin_bytes, uint32_t* order, uint64_t* group_offsets);
+int cld_group_by_language_device(int device, const cld_result* d_results, size_t n, uint32_t group_flags,
+                                 const uint64_t* d_offsets, uint64_t* d_counts, uint64_t* d_bin_bytes,
+                                 uint32_t* d_order, uint64_t* d_group_offsets, void* d_work, size_t work_bytes,
+                                 void* stream);
+int cld_gather_docs_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n_src,
+                           const uint32_t* d_index, size_t m, uint8_t* d_out_buf, uint64_t out_cap,
+                           uint64_t* d_out_offsets, void* d_work, size_t work_bytes, void* stream);
+
 /* ExtDetectLanguageSummary with a ResultChunkVector per document
  * (compact_lang_det.h:324-335): the same results as cld_detect_batch_ex plus
  * each document's chunk vector -- pieces of the document as given, in one

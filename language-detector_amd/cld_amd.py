@@ -13,6 +13,9 @@ Mirrors the reference's caller-facing interface for this path:
   detect_batch(docs, flags=FLAG_SCRUB_UTF8)   ill-formed bytes repaired (each error position of the
                                           check becomes a space) and every document scored
   scrub_utf8_batch(docs)                  that repair alone, as a GPU kernel -> (buffer, replaced)
+  group_by_language(results)              counts, stable order and group offsets per language (host reference)
+  group_by_language_device / gather_docs_device   the same over results in HBM, and the chosen
+                                          documents packed into a new device batch
   detect_language_scrubbed(text)          the repair on the host, then detect_language
 There is no CPU fallback: if the HIP library or a GPU is missing, calls raise.
 """
@@ -41,6 +44,12 @@ UNKNOWN_ENCODING = 23      # encodings.h UNKNOWN_ENCODING
 UNKNOWN_LANGUAGE = 26      # generated_language.h UNKNOWN_LANGUAGE
 LANG_FAILED = 0xFFFF       # include/cld_mi355x.h CLD_LANG_FAILED: a document without a result
 EIO, ENOMEM, ENOSPC, EINVAL = -5, -12, -28, -22   # include/cld_mi355x.h error codes
+NUM_LANGUAGES = 614        # include/cld_mi355x.h CLD_NUM_LANGUAGES: Language values 0..613
+GROUP_BINS = 615           # include/cld_mi355x.h CLD_GROUP_BINS: bin 614 takes every key >= 614 (LANG_FAILED too)
+GROUP_TOP1 = 1             # include/cld_mi355x.h CLD_GROUP_TOP1: the key is lang3[0], not summary_lang
+GROUP_RELIABLE_ONLY = 2    # include/cld_mi355x.h CLD_GROUP_RELIABLE_ONLY: unreliable documents get key UNKNOWN_LANGUAGE
+GROUP_WGS = 256            # csrc/cld_kernels.h kGroupWgs: the group entries cut a batch into at most this many ranges
+GROUP_TILE = 512           # csrc/cld_kernels.h kGroupTile: documents per step of a range's workgroup
 
 RESULT_DTYPE = np.dtype([("lang3", "<u2", 3), ("summary_lang", "<u2"), ("percent3", "i1", 3),
                          ("is_reliable", "u1"), ("text_bytes", "<i4"), ("normalized3", "<f8", 3)])
@@ -59,7 +68,8 @@ EXPORTS = ("detect_language", "cld_init", "cld_init_device", "cld_shutdown", "cl
            "cld_detect_batch_device_hints", "cld_detect_batch_device_vec", "cld_detect_batch_docflags",
            "cld_detect_batch_vec_docflags", "cld_detect_batch_device_docflags",
            "cld_detect_batch_device_vec_docflags", "cld_scrub_utf8_host", "cld_scrub_utf8_batch",
-           "cld_scrub_utf8_device", "detect_language_scrubbed")
+           "cld_scrub_utf8_device", "detect_language_scrubbed", "cld_group_work_bytes", "cld_group_by_language",
+           "cld_group_by_language_device", "cld_gather_docs_device")
 CHUNK_DTYPE = np.dtype([("offset", "<i4"), ("bytes", "<i4"), ("lang1", "<u2"), ("pad", "<u2")])   # cld_chunk
 
 
@@ -211,6 +221,11 @@ def lib():
         L.cld_scrub_utf8_device.argtypes = [ctypes.c_int, vp, vp, sz, vp, vp, vp]
         L.detect_language_scrubbed.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
         L.detect_language_scrubbed.restype = ctypes.c_char_p
+        L.cld_group_work_bytes.argtypes = [sz]
+        L.cld_group_work_bytes.restype = sz
+        L.cld_group_by_language.argtypes = [vp, sz, u32, vp, vp, vp, vp, vp]
+        L.cld_group_by_language_device.argtypes = [ctypes.c_int, vp, sz, u32, vp, vp, vp, vp, vp, vp, sz, vp]
+        L.cld_gather_docs_device.argtypes = [ctypes.c_int, vp, vp, sz, vp, sz, vp, u64, vp, vp, sz, vp]
         _lib = L
     return _lib
 
@@ -640,6 +655,64 @@ def scrub_utf8_device(device, d_buf_ptr, d_offsets_ptr, n, d_out_ptr, d_replaced
     rc = lib().cld_scrub_utf8_device(device, d_buf_ptr, d_offsets_ptr, n, d_out_ptr, d_replaced_ptr, stream_ptr)
     if rc != 0:
         raise CldError("cld_scrub_utf8_device failed: %d" % rc)
+
+
+def group_range(n):
+    """Documents per workgroup range of the group entries for n documents (csrc/cld_kernels.h cld_group_range)."""
+    per = -(-n // GROUP_WGS)
+    return max(GROUP_TILE, -(-per // GROUP_TILE) * GROUP_TILE)
+
+
+def group_work_bytes(n):
+    """cld_group_work_bytes: the workspace either device entry needs for n documents."""
+    return int(lib().cld_group_work_bytes(n))
+
+
+def group_by_language(results, offsets=None, flags=0):
+    """cld_group_by_language (the host reference, no GPU) over a RESULT_DTYPE array -> dict of
+    counts uint64[GROUP_BINS], group_offsets uint64[GROUP_BINS + 1], order uint32[n] (document
+    indices sorted by (bin, index)) and, with offsets, bin_bytes uint64[GROUP_BINS].
+    flags: GROUP_TOP1 | GROUP_RELIABLE_ONLY."""
+    results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
+    n = len(results)
+    got = {"counts": np.zeros(GROUP_BINS, np.uint64), "group_offsets": np.zeros(GROUP_BINS + 1, np.uint64),
+           "order": np.zeros(n, np.uint32)}
+    optr = bptr = None
+    if offsets is not None:
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if len(offsets) != n + 1:
+            raise ValueError("need n + 1 offsets")
+        got["bin_bytes"] = np.zeros(GROUP_BINS, np.uint64)
+        optr, bptr = offsets.ctypes.data, got["bin_bytes"].ctypes.data
+    rc = lib().cld_group_by_language(results.ctypes.data, n, flags, optr, got["counts"].ctypes.data, bptr,
+                                     got["order"].ctypes.data, got["group_offsets"].ctypes.data)
+    if rc != 0:
+        raise CldError("cld_group_by_language failed: %d" % rc)
+    return got
+
+
+def group_by_language_device(device, d_results_ptr, n, d_counts_ptr, d_work_ptr, work_bytes, flags=0,
+                             d_offsets_ptr=None, d_bin_bytes_ptr=None, d_order_ptr=None, d_group_offsets_ptr=None,
+                             stream_ptr=None):
+    """cld_group_by_language_device: every pointer in device memory (results cld_result[n],
+    counts / bin_bytes uint64[GROUP_BINS], order uint32[n], group_offsets uint64[GROUP_BINS + 1],
+    a workspace of group_work_bytes(n)); asynchronous on the stream."""
+    rc = lib().cld_group_by_language_device(device, d_results_ptr, n, flags, d_offsets_ptr, d_counts_ptr,
+                                            d_bin_bytes_ptr, d_order_ptr, d_group_offsets_ptr, d_work_ptr, work_bytes,
+                                            stream_ptr)
+    if rc != 0:
+        raise CldError("cld_group_by_language_device failed: %d" % rc)
+
+
+def gather_docs_device(device, d_buf_ptr, d_offsets_ptr, n_src, d_index_ptr, m, d_out_buf_ptr, out_cap,
+                       d_out_offsets_ptr, d_work_ptr, work_bytes, stream_ptr=None):
+    """cld_gather_docs_device: documents d_index[0..m) of the device batch packed into
+    (d_out_buf, d_out_offsets uint64[m + 1]); out_cap 0 with no buffer sizes the output.
+    A workspace of group_work_bytes(m); asynchronous on the stream."""
+    rc = lib().cld_gather_docs_device(device, d_buf_ptr, d_offsets_ptr, n_src, d_index_ptr, m, d_out_buf_ptr, out_cap,
+                                      d_out_offsets_ptr, d_work_ptr, work_bytes, stream_ptr)
+    if rc != 0:
+        raise CldError("cld_gather_docs_device failed: %d" % rc)
 
 
 def valid_prefix_host(doc):

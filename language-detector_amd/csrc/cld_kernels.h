@@ -207,6 +207,27 @@ hipError_t cld_launch_valid_copy(const uint8_t* buf, const uint64_t* offs, int n
                                  uint8_t* out, uint64_t bytes_hint, hipStream_t s);
 hipError_t cld_launch_valid_fixup(const uint64_t* offs, int n, const int32_t* valid_prefix, cld_result* out,
                                   int32_t* n_chunks, uint32_t unknown_language, hipStream_t s);
+// cld_group_by_language_device / cld_gather_docs_device (cld_group.hip).  Both
+// cut their n items into at most kGroupWgs contiguous ranges of
+// cld_group_range(n) items, a multiple of kGroupTile, one workgroup each, so
+// `work` (kGroupWorkBytes, 8-byte aligned, not zeroed) does not grow with n:
+// per-range histograms (u32) and byte totals (u64) over the bins, the counts;
+// the gather keeps its per-range sums there.  n, m <= INT32_MAX.
+// cld_launch_group: counts, bin_bytes (with offs), order, group_offsets each
+// nullable.  cld_launch_gather: out_offs[0..m] always, out[0, min(total, cap))
+// when cap > 0.
+constexpr int kGroupWgs = 256;
+constexpr int kGroupTile = 512;
+constexpr size_t kGroupWorkBytes = (size_t)kGroupWgs * CLD_GROUP_BINS * (sizeof(uint32_t) + sizeof(uint64_t)) +
+                                   (CLD_GROUP_BINS + 1) * sizeof(uint64_t);
+inline uint32_t cld_group_range(uint32_t n) {
+  const uint32_t per = n / kGroupWgs + (n % kGroupWgs != 0);
+  return per <= (uint32_t)kGroupTile ? (uint32_t)kGroupTile : (per + kGroupTile - 1) / kGroupTile * kGroupTile;
+}
+hipError_t cld_launch_group(const cld_result* res, uint32_t n, uint32_t flags, const uint64_t* offs, uint64_t* counts,
+                            uint64_t* bin_bytes, uint32_t* order, uint64_t* group_offsets, void* work, hipStream_t s);
+hipError_t cld_launch_gather(const uint8_t* buf, const uint64_t* offs, uint32_t n_src, const uint32_t* index, uint32_t m,
+                             uint8_t* out, uint64_t cap, uint64_t* out_offs, void* work, hipStream_t s);
 // ApplyHints (cld_hints.hip; compact_lang_det_impl.cc:1587-1684), one wave
 // per document: priors14 (14 per document, trimmed to 4, zero-padded),
 // boosts16 (the 16 langprobs enqueue() takes as `priors`) and special (the

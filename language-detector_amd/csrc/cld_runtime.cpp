@@ -2609,6 +2609,87 @@ int cld_scrub_utf8_batch(const uint8_t* buf, const uint64_t* offsets, size_t n, 
   return CLD_OK;
 }
 
+size_t cld_group_work_bytes(size_t n) {
+  (void)n;   // a fixed number of workgroup ranges whatever n is (cld_kernels.h)
+  return kGroupWorkBytes;
+}
+
+// The host reference of the group entries: a counting sort, document by document.
+int cld_group_by_language(const cld_result* results, size_t n, uint32_t group_flags, const uint64_t* offsets,
+                          uint64_t* counts, uint64_t* bin_bytes, uint32_t* order, uint64_t* group_offsets) {
+  if ((group_flags & ~(CLD_GROUP_TOP1 | CLD_GROUP_RELIABLE_ONLY)) != 0 || n > 0x7FFFFFFFu || (bin_bytes && !offsets) ||
+      (n > 0 && (!results || !counts)))
+    return CLD_EINVAL;
+  auto bin_of = [&](size_t i) -> uint32_t {
+    uint32_t key = (group_flags & CLD_GROUP_TOP1) ? results[i].lang3[0] : results[i].summary_lang;
+    if ((group_flags & CLD_GROUP_RELIABLE_ONLY) && results[i].is_reliable == 0) key = 26;   // UNKNOWN_LANGUAGE
+    return std::min<uint32_t>(key, CLD_NUM_LANGUAGES);
+  };
+  uint64_t cnt[CLD_GROUP_BINS] = {0}, at[CLD_GROUP_BINS + 1];
+  if (bin_bytes) std::fill(bin_bytes, bin_bytes + CLD_GROUP_BINS, 0);
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t b = bin_of(i);
+    ++cnt[b];
+    if (bin_bytes) bin_bytes[b] += offsets[i + 1] - offsets[i];
+  }
+  at[0] = 0;
+  for (uint32_t b = 0; b < CLD_GROUP_BINS; ++b) at[b + 1] = at[b] + cnt[b];
+  if (counts) std::copy(cnt, cnt + CLD_GROUP_BINS, counts);
+  if (group_offsets) std::copy(at, at + CLD_GROUP_BINS + 1, group_offsets);
+  if (order)
+    for (size_t i = 0; i < n; ++i) order[at[bin_of(i)]++] = (uint32_t)i;
+  return CLD_OK;
+}
+
+int cld_group_by_language_device(int device, const cld_result* d_results, size_t n, uint32_t group_flags,
+                                 const uint64_t* d_offsets, uint64_t* d_counts, uint64_t* d_bin_bytes,
+                                 uint32_t* d_order, uint64_t* d_group_offsets, void* d_work, size_t work_bytes,
+                                 void* stream) {
+  if ((group_flags & ~(CLD_GROUP_TOP1 | CLD_GROUP_RELIABLE_ONLY)) != 0 || n > 0x7FFFFFFFu ||
+      (d_bin_bytes && !d_offsets) || (n > 0 && (!d_results || !d_counts || !d_work || ((uintptr_t)d_work & 7))))
+    return CLD_EINVAL;
+  if (n > 0 && work_bytes < cld_group_work_bytes(n)) return CLD_ENOSPC;
+  int rc = cld_init(nullptr, 0);
+  if (rc) return rc;
+  if (device < 0 || device >= (int)g_devs.size()) return CLD_EINVAL;
+  Device* d = g_devs[device];
+  HIP_OK(hipSetDevice(d->id));
+  hipStream_t s = stream ? (hipStream_t)stream : d->stream;
+  if (n == 0) {
+    if (d_counts) HIP_OK(hipMemsetAsync(d_counts, 0, CLD_GROUP_BINS * sizeof(uint64_t), s));
+    if (d_bin_bytes) HIP_OK(hipMemsetAsync(d_bin_bytes, 0, CLD_GROUP_BINS * sizeof(uint64_t), s));
+    if (d_group_offsets) HIP_OK(hipMemsetAsync(d_group_offsets, 0, (CLD_GROUP_BINS + 1) * sizeof(uint64_t), s));
+    return CLD_OK;
+  }
+  // (no scratch of the context is used: nothing to serialise with other batches)
+  HIP_OK(cld_launch_group(d_results, (uint32_t)n, group_flags, d_offsets, d_counts, d_bin_bytes, d_order,
+                          d_group_offsets, d_work, s));
+  return CLD_OK;
+}
+
+int cld_gather_docs_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n_src,
+                           const uint32_t* d_index, size_t m, uint8_t* d_out_buf, uint64_t out_cap,
+                           uint64_t* d_out_offsets, void* d_work, size_t work_bytes, void* stream) {
+  if (m > 0x7FFFFFFFu || n_src > 0x7FFFFFFFu || (out_cap > 0 && !d_out_buf) ||
+      (m > 0 && (!d_index || !d_out_offsets || !d_work || ((uintptr_t)d_work & 7) ||
+                 (n_src > 0 && (!d_buf || !d_offsets)))))
+    return CLD_EINVAL;
+  if (m > 0 && work_bytes < cld_group_work_bytes(m)) return CLD_ENOSPC;
+  int rc = cld_init(nullptr, 0);
+  if (rc) return rc;
+  if (device < 0 || device >= (int)g_devs.size()) return CLD_EINVAL;
+  Device* d = g_devs[device];
+  HIP_OK(hipSetDevice(d->id));
+  hipStream_t s = stream ? (hipStream_t)stream : d->stream;
+  if (m == 0) {
+    if (d_out_offsets) HIP_OK(hipMemsetAsync(d_out_offsets, 0, sizeof(uint64_t), s));
+    return CLD_OK;
+  }
+  HIP_OK(cld_launch_gather(d_buf, d_offsets, (uint32_t)n_src, d_index, (uint32_t)m, d_out_buf, out_cap, d_out_offsets,
+                           d_work, s));
+  return CLD_OK;
+}
+
 int cld_detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
                          uint32_t flags, cld_result* out, cld_chunk* chunks, size_t chunk_cap,
                          uint64_t* chunk_offsets) {
