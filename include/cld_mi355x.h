@@ -638,6 +638,44 @@ typedef struct cld_batch_stats {
 } cld_batch_stats;
 int cld_last_batch_stats(int device, cld_batch_stats* st);
 
+/* Which long-document kernels scored the batch cld_last_batch_stats speaks of
+ * (read-only; the list counts the staged kernels keep on the device, summed
+ * over the chunks of a host batch like cld_batch_stats).  A long document is
+ * one k_wave did not finish.  The staged path stores its pass-1 spans and
+ * scores it whole (k_lscore) or, with many spans, in groups of 16 spans
+ * (k_lgroup / k_lfinish); what it cannot take -- the Squeeze restart, a block
+ * wider than its 2 KB window, no room in the store or the group list, records
+ * that outgrew their room -- the fused k_long redoes from scratch.
+ *   long_list      documents on the long list
+ *   staged_whole   stored, pass 1 scored whole
+ *   staged_split1  stored, pass 1 scored in groups;  groups1: the groups asked
+ *                  for, those of a document that found no room in the group
+ *                  list included (groups2 likewise)
+ *   staged_pass2   stored documents whose pass 1 was not good enough (whole
+ *                  and split ones); staged_split2 / groups2: the split ones
+ *                  among them and their pass-2 groups
+ *   to_fused       documents the staged kernels handed to the fused k_long,
+ *                  at any stage (a list of at most 64 long documents that
+ *                  reaches the staged kernels goes there whole)
+ *   store_units    16-byte units of the span store asked for (over the
+ *                  store's size: it ran out)
+ *   spec_taken     speculative pass-2 results the fused kernel took
+ * long_list == staged_whole + staged_split1 + (documents handed on by the
+ * span stage); to_fused also counts the later stages' hand-ons.
+ * Where the runtime skipped the staged launches altogether -- the host path
+ * with at most 64 documents of more than 256 bytes in a chunk, none of them
+ * over the fused kernel's 1 MB cap or CLD_LONG_SMALL_KB; the vector entries;
+ * diagnostics; CLD_LONG_STAGED=0 -- every field from staged_whole to store_units reads 0
+ * and the fused kernel scored the whole list.  A call k_wave finished alone
+ * reads all zeros.  CLD_EINVAL: no such device (before cld_init), st NULL.
+ * Not updated by the device-resident vector and group entries. */
+typedef struct cld_route_stats {
+  uint64_t long_list, staged_whole, staged_split1, groups1, staged_pass2, staged_split2, groups2, to_fused,
+      store_units, spec_taken;
+  uint64_t reserved[6];
+} cld_route_stats;
+int cld_last_route_stats(int device, cld_route_stats* st);
+
 /* ---- Run-time table loading (CLD2 dynamic data, cld2_dynamic_data.h:22-147).
  * A "cld2_data_file00" image carries the scoring tables of ScoringTables
  * (CJK unigram machine, kAvgDeltaOctaScore, compat/deltabi/distinctbi/quad/

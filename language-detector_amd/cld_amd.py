@@ -69,7 +69,7 @@ EXPORTS = ("detect_language", "cld_init", "cld_init_device", "cld_shutdown", "cl
            "cld_detect_batch_vec_docflags", "cld_detect_batch_device_docflags",
            "cld_detect_batch_device_vec_docflags", "cld_scrub_utf8_host", "cld_scrub_utf8_batch",
            "cld_scrub_utf8_device", "detect_language_scrubbed", "cld_group_work_bytes", "cld_group_by_language",
-           "cld_group_by_language_device", "cld_gather_docs_device")
+           "cld_group_by_language_device", "cld_gather_docs_device", "cld_last_route_stats")
 CHUNK_DTYPE = np.dtype([("offset", "<i4"), ("bytes", "<i4"), ("lang1", "<u2"), ("pad", "<u2")])   # cld_chunk
 
 
@@ -127,6 +127,16 @@ class BatchStats(ctypes.Structure):
                 ("long_requeue", ctypes.c_uint64 * 8)]
 
 
+class RouteStats(ctypes.Structure):
+    """include/cld_mi355x.h cld_route_stats: which long-document kernels scored the last batch."""
+    FIELDS = ("long_list", "staged_whole", "staged_split1", "groups1", "staged_pass2", "staged_split2", "groups2",
+              "to_fused", "store_units", "spec_taken")
+    _fields_ = [(f, ctypes.c_uint64) for f in FIELDS] + [("reserved", ctypes.c_uint64 * 6)]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f in self.FIELDS}
+
+
 class CldError(RuntimeError):
     pass
 
@@ -166,6 +176,7 @@ def lib():
         L.cld_language_name.restype = ctypes.c_char_p
         L.cld_version.restype = ctypes.c_char_p
         L.cld_last_batch_stats.argtypes = [ctypes.c_int, ctypes.POINTER(BatchStats)]
+        L.cld_last_route_stats.argtypes = [ctypes.c_int, ctypes.POINTER(RouteStats)]
         L.cld_init_device.argtypes = [ctypes.c_char_p, ctypes.c_int]
         L.cld_plan_shards.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
         L.cld_kernel_time.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double),
@@ -592,6 +603,15 @@ def last_stats(device=0):
     rc = lib().cld_last_batch_stats(device, ctypes.byref(st))
     if rc != 0:
         raise CldError("cld_last_batch_stats failed: %d" % rc)
+    return st
+
+
+def last_route_stats(device=0):
+    """The routes the last batch's long documents took (RouteStats; cld_last_route_stats)."""
+    st = RouteStats()
+    rc = lib().cld_last_route_stats(device, ctypes.byref(st))
+    if rc != 0:
+        raise CldError("cld_last_route_stats failed: %d" % rc)
     return st
 
 

@@ -534,6 +534,7 @@ struct Device {
   const uint8_t* p_buf = nullptr; const uint64_t* p_offs = nullptr; uint64_t p_base = 0;
   const uint64_t* chk_offs = nullptr; const int32_t* chk_vp = nullptr;
   cld_batch_stats last{};
+  cld_route_stats last_route{};   // the same batch's long-document routes (cld_last_route_stats)
   uint64_t last_n = 0;
   bool stats_pending = false;
   // Streamed host path (run_host_shard): two chunk slots, each with pinned
@@ -1024,7 +1025,20 @@ int enqueue(Device* d, const uint8_t* buf, const uint64_t* offs, size_t n, cld_r
 // short_docs: finished by k_wave; long_docs: by k_long (or the staged path)
 // on the parallel span builder; general_docs: by k_long on the sequential
 // span source (cld_seq.hip).
-void add_counters(const uint32_t* c, uint64_t docs, cld_batch_stats* st) {
+// rt: the routes its long documents took (cld_route_stats), from the list
+// counts the staged kernels keep; a batch whose staged launches were skipped
+// leaves those words at their per-batch zero.
+void add_counters(const uint32_t* c, uint64_t docs, cld_batch_stats* st, cld_route_stats* rt) {
+  rt->long_list += c[kCtrRequeue];
+  rt->staged_whole += (uint64_t)c[kCtrStOk] + c[kCtrStOkH];
+  rt->staged_split1 += c[kCtrStPar1];
+  rt->groups1 += c[kCtrStG1];
+  rt->staged_pass2 += (uint64_t)c[kCtrStP2] + c[kCtrStP2H];
+  rt->staged_split2 += c[kCtrStPar2];
+  rt->groups2 += c[kCtrStG2];
+  rt->to_fused += c[kCtrStFall];
+  rt->store_units += c[kCtrStPool];
+  rt->spec_taken += c[kCtrSpecTake];
   const uint64_t shorts = docs - c[kCtrRequeue];
   st->docs += docs;
   st->general_docs += c[kCtrSeq];
@@ -1053,7 +1067,8 @@ int collect_stats(Device* d) {
   HIP_OK(hipEventElapsedTime(&ms3, d->ev[2], d->ev[3]));
   cld_batch_stats& st = d->last;
   memset(&st, 0, sizeof(st));
-  add_counters(c, d->last_n, &st);
+  d->last_route = cld_route_stats{};
+  add_counters(c, d->last_n, &st, &d->last_route);
   st.short_ms = ms1;
   st.long_ms = ms2;
   st.general_ms = ms3;
@@ -1483,9 +1498,10 @@ int run_host_stream(Device* d, const Batch& b, cld_batch_stats* st_out) {
   // statistics of the whole call: counters summed over chunks, kernel time over launches
   cld_batch_stats& st = d->last;
   memset(&st, 0, sizeof(st));
+  d->last_route = cld_route_stats{};
   bool err = false;
   for (size_t c = 0; c < nch; ++c) {
-    add_counters(d->h_ctr + c * kCtrSlots, cut[c + 1] - cut[c], &st);
+    add_counters(d->h_ctr + c * kCtrSlots, cut[c + 1] - cut[c], &st, &d->last_route);
     err |= d->h_ctr[c * kCtrSlots + kCtrError] != 0;
   }
   for (size_t i = 0; i < d->ev_used; ++i) {
@@ -1618,7 +1634,7 @@ int run_tiny(Device* d, const Batch& b) {
   if (rc != CLD_OK && rc != kDocsFailed) return rc;
   if (st.docs == st.short_docs) {
     std::unique_lock<std::mutex> dl(d->mu, std::try_to_lock);   // best effort: diagnostics only
-    if (dl.owns_lock()) { d->last = st; d->stats_pending = false; }
+    if (dl.owns_lock()) { d->last = st; d->last_route = cld_route_stats{}; d->stats_pending = false; }
   } else {
     std::lock_guard<std::mutex> dl(d->mu);
     d->last = st;
@@ -1716,6 +1732,7 @@ int run_vec_shard(Device* d, const Batch& b, std::vector<cld_chunk>* chunks, std
   // or an offset map), the vectors to ch in document order.
   std::vector<uint64_t> pool_off, pos;
   cld_batch_stats vst{};
+  cld_route_stats vrt{};   // (k_long<VEC> takes the whole list: no staged launches)
   auto sub = [&](const Batch& sb, bool big, std::vector<int32_t>& nch, std::vector<cld_chunk>& ch) -> int {
     const uint64_t* o = sb.offs;
     const size_t m = sb.n;
@@ -1797,6 +1814,8 @@ int run_vec_shard(Device* d, const Batch& b, std::vector<cld_chunk>* chunks, std
     vst.long_docs += m - ctr[kCtrSeq];
     for (int k = 0; k < 3; ++k) vst.passes[k] += ctr[kCtrPass1 + k];
     vst.passes[3] += ctr[kCtrError];
+    vrt.long_list += ctr[kCtrRequeue];
+    vrt.spec_taken += ctr[kCtrSpecTake];
     pos.assign(m, 0);
     uint64_t total = 0;
     for (size_t i = 0; i < m; ++i) {
@@ -1862,6 +1881,7 @@ int run_vec_shard(Device* d, const Batch& b, std::vector<cld_chunk>* chunks, std
     a += m;
   }
   d->last = vst;
+  d->last_route = vrt;
   d->stats_pending = false;
   return failed ? CLD_EIO : CLD_OK;
 }
@@ -3022,6 +3042,16 @@ int cld_last_batch_stats(int device, cld_batch_stats* st) {
   HIP_OK(hipSetDevice(d->id));
   int rc = collect_stats(d);
   *st = d->last;
+  return rc;
+}
+
+int cld_last_route_stats(int device, cld_route_stats* st) {
+  if (device < 0 || device >= (int)g_devs.size() || !st) return CLD_EINVAL;
+  Device* d = g_devs[device];
+  std::lock_guard<std::mutex> lk(d->mu);
+  HIP_OK(hipSetDevice(d->id));
+  int rc = collect_stats(d);
+  *st = d->last_route;
   return rc;
 }
 

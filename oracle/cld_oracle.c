@@ -1280,6 +1280,9 @@ struct cldo_ctx {
   rvec_t* vec;                                 /* ResultChunkVector being built, or NULL */
   offmap_t map_orig, map_low;                  /* the scanner's maps (vec mode) */
   int cflags;                                  /* the caller's flags (ExtDetectLanguageSummary `flags`) */
+  /* what the first pass of the last document did (cldo_first_pass): spans the scanner returned,
+   * the longest span's text bytes, the Squeeze restart taken, a second pass asked for */
+  int p1_spans, p1_max_tb, p1_squeeze, p1_recurse;
 };
 
 static void tracef(struct cldo_ctx* c, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -2111,6 +2114,7 @@ static int detect_summary_v2(struct cldo_ctx* c, const uint8_t* buf, int len, cl
   const int unk = (int)T.meta.unknown_language;
   int flags = c->cflags & (kCLDFlagScoreAsQuads | kCLDFlagBestEffort);   /* the caller's flags (:1707) */
   r->passes = 0;
+  c->p1_spans = c->p1_max_tb = c->p1_squeeze = c->p1_recurse = 0;
   for (;;) {
     r->passes++;
     for (int i = 0; i < 3; ++i) { r->lang3[i] = (uint16_t)unk; r->percent3[i] = 0; r->normalized3[i] = 0.0; }
@@ -2153,6 +2157,7 @@ static int detect_summary_v2(struct cldo_ctx* c, const uint8_t* buf, int len, cl
       } else if ((kCheapSqueezeTestThresh >> 1) < span.text_bytes && !(flags & kCLDFlagFinish)) {
         if (cheap_squeeze_trigger_test(span.text, span.text_bytes, kCheapSqueezeTestLen, c->sqz_tbl)) {
           flags |= kCLDFlagSqueeze; restart = 1;
+          if (r->passes == 1) c->p1_squeeze = 1;
           if (c->trace) tracef(c, "restart squeeze");
           break;
         }
@@ -2161,6 +2166,10 @@ static int detect_summary_v2(struct cldo_ctx* c, const uint8_t* buf, int len, cl
         span.text_bytes = c->vec ? cheap_rep_words_inplace_overwrite(span.text, span.text_bytes, &hash, c->predict)
                                  : cheap_rep_words_inplace(span.text, span.text_bytes, &hash, c->predict);
       cx.ulscript = span.ulscript;
+      if (r->passes == 1) {
+        c->p1_spans++;
+        if (span.text_bytes > c->p1_max_tb) c->p1_max_tb = span.text_bytes;
+      }
       score_one_script_span(c, &cx, &span, &dt);
       total += span.text_bytes;
     }
@@ -2204,6 +2213,7 @@ static int detect_summary_v2(struct cldo_ctx* c, const uint8_t* buf, int len, cl
       return summary;
     }
     if (c->trace) tracef(c, "recurse total=%d", total);
+    c->p1_recurse = 1;
     flags |= kCLDFlagTop40 | kCLDFlagRepeats | kCLDFlagFinish;
     if (total < kShortTextThresh) flags |= kCLDFlagShort | kCLDFlagUseWords;
   }
@@ -2225,6 +2235,9 @@ void cldo_ctx_free(cldo_ctx* c) {
 void cldo_set_trace(cldo_ctx* c, cldo_trace_fn fn, void* arg) { c->trace = fn; c->trace_arg = arg; }
 void cldo_set_trace_text(cldo_ctx* c, int on) { c->trace_text = on; }
 void cldo_set_flags(cldo_ctx* c, int flags) { c->cflags = flags; }
+void cldo_first_pass(const cldo_ctx* c, int out[4]) {
+  out[0] = c->p1_spans; out[1] = c->p1_max_tb; out[2] = c->p1_squeeze; out[3] = c->p1_recurse;
+}
 
 /* The document is copied into a buffer followed by 16 NUL bytes, matching
  * the NUL-terminated C string the reference wrapper receives. */

@@ -52,6 +52,10 @@ int cldo_detect_batch_ex(const char* buf, const uint64_t* offsets, int n, const 
 /* The caller's ExtDetectLanguageSummary flags (compact_lang_det.h:343-349):
  * 0x0100 kCLDFlagScoreAsQuads, 0x4000 kCLDFlagBestEffort; others ignored. */
 void cldo_set_flags(cldo_ctx* c, int flags);
+/* The first pass of the context's last document: out[0] script spans the scanner returned (up to the
+ * Squeeze restart, if taken), out[1] the longest one's text bytes, out[2] the Squeeze restart taken in
+ * pass 1, out[3] some pass was not good enough (another pass with Repeats followed). */
+void cldo_first_pass(const cldo_ctx* c, int out[4]);
 int cldo_detect_batch_flags(const char* buf, const uint64_t* offsets, int n, const uint8_t* plain,
                             const uint32_t* priors, cldo_result* out, int threads, int flags);
 /* handlers.go:150-151 text preparation: flags 1 = StripExtras, 2 = C-string cut.

@@ -92,6 +92,20 @@ class Oracle:
             return lang, r, lines
         return lang, r
 
+    def first_pass(self, text, flags=0):
+        """(spans, longest span's text bytes, Squeeze restart in pass 1, a pass with Repeats followed)
+        of one plain-text document: what the trace shows of its passes, without the trace."""
+        b = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+        self.lib.cldo_set_flags.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        self.lib.cldo_first_pass.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int * 4)]
+        self.lib.cldo_set_flags(self.ctx, int(flags))
+        r = Result()
+        self.lib.cldo_detect(self.ctx, b, len(b), ctypes.byref(r))
+        self.lib.cldo_set_flags(self.ctx, 0)
+        out = (ctypes.c_int * 4)()
+        self.lib.cldo_first_pass(self.ctx, ctypes.byref(out))
+        return out[0], out[1], bool(out[2]), bool(out[3])
+
     def detect_language(self, text):
         """wrapper.cc:7-16 semantics: strlen, UNKNOWN -> 'en'."""
         b = text.encode("utf-8") if isinstance(text, str) else bytes(text)

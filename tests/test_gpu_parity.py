@@ -222,6 +222,10 @@ got = cld_amd.detect_batch(buf=b3, offsets=o3)
 assert_same(got, want, "c3 staged")
 st = cld_amd.last_stats(0)
 assert st.general_docs == 0 and st.long_docs == 20000, (st.general_docs, st.long_docs)
+rt = cld_amd.last_route_stats(0).as_dict()
+# a 1 MB store: 65,536 units of 16 bytes, fewer than the batch asks for, and what found no room went to the fused kernel
+assert rt["store_units"] > (1 << 20) // 16 and rt["to_fused"] > 0, rt
+assert rt["long_list"] == 20000 and rt["staged_whole"] + rt["staged_split1"] > 0, rt
 print("staged ok", st.passes[0], st.passes[1])
 '''
 
@@ -232,7 +236,8 @@ def test_staged_long_path_and_its_hand_ons(gpu, oracle):
     k_lgroup / k_lfinish) and the documents it hands to the fused k_long: a
     span block wider than its 2 KB LDS window (a 3 KB word), hundreds of
     spans (span-parallel, passes 1 and 2), more than 1,024 spans, the Squeeze
-    restart, pass 2 with Repeats -- in one batch large enough to take the
+    restart, pass 2 with Repeats, each on the route the oracle's first pass
+    and the documented thresholds give it (cld_last_route_stats) -- in one batch large enough to take the
     staged path (more than 4 documents per fused wave), all equal to the
     oracle and none on the sequential span source.
     Then the store exhausted (CLD_LONG_STORE_MB=1, child process): every
@@ -242,10 +247,15 @@ def test_staged_long_path_and_its_hand_ons(gpu, oracle):
     b3, o3 = corpus.c3(17000, seed=172, page=2048)
     docs = [bytes(b3[o3[i]:o3[i + 1]]) for i in range(17000)]
     b2, o2 = corpus.c2(3000, seed=173)
-    docs[5] = b"x" * 3000 + b" " + bytes(b2[o2[0]:o2[40]])                  # one 3 KB word
+    # one 3 KB word (of random letters: 3000 equal ones, as this read before, take the Squeeze restart
+    # in k_lspan and never meet the window)
+    docs[5] = bytes(np.random.default_rng(176).integers(97, 123, size=3000).astype(np.uint8)) + b" " + \
+        bytes(b2[o2[0]:o2[40]])
     docs[9] = " ".join(["ab", "где", "xy", "कि"] * 300).encode()             # ~1200 spans
     docs[11] = ("abc дом " * 500).encode()                                      # many two-script spans (span-parallel)
-    docs[13] = corpus.BOILERPLATE * 20 + bytes(b2[o2[0]:o2[30]])             # the Squeeze restart
+    # the Squeeze restart: a repetitive span of more than 2048 text bytes (20 repeats, as this read before, make
+    # a 503-byte span, which never takes CheapSqueezeTriggerTest: the route counts below showed it)
+    docs[13] = corpus.BOILERPLATE * 100 + bytes(b2[o2[0]:o2[30]])
     # span-parallel documents (more than 48 spans, cld_long.hip "span-parallel
     # scoring"): the words of 16 KB four-script pages shuffled, so scripts
     # alternate every word or few -- hundreds of spans, pass 1 and pass 2
@@ -261,6 +271,33 @@ def test_staged_long_path_and_its_hand_ons(gpu, oracle):
     st = gpu.last_stats(0)
     assert st.general_docs == 0, list(st.long_requeue)
     assert st.passes[1] > 1000                                                # pass 2 (Repeats) taken
+    # the routes the docstring names, from the oracle's first pass of every document and the thresholds in
+    # the source comments (long_route_model): the shuffled pages of more than one script (three quarters of
+    # the 400; a one-script page stays one span however its words are shuffled, and is scored whole through
+    # the 2 KB window), docs[9] and docs[11] are split in pass 1, the split ones that need Repeats again in
+    # pass 2; the 3 KB word (stored, then handed on by the scoring stage) and docs[13] (handed on by the
+    # span stage) go to the fused kernel
+    import long_route_model as lrm
+    facts = [lrm.Facts(oracle, d) for d in docs]
+    named = [5, 9, 11, 13] + [20 + 7 * k for k in range(400)]
+    pages = [facts[20 + 7 * k] for k in range(400)]
+    assert sum(f.nsp > lrm.PAR_MIN for f in pages) >= 300 and not any(f.squeeze1 for f in pages)
+    assert not facts[5].squeeze1 and facts[5].max_tb > 3000 and facts[13].squeeze1 and facts[9].nsp > 1024 and facts[11].nsp == 1000
+    # (no other document holds a word that could be wider than a window block: nothing the model cannot see)
+    assert all(max(map(len, d.split())) < 256 for i, d in enumerate(docs) if i != 5)
+    rt = gpu.last_route_stats(0).as_dict()
+    want = lrm.expected_routes(docs, facts, wide={5})
+    assert {f: rt[f] for f in lrm.FIELDS} == want, (rt, want)
+    assert want["staged_split1"] >= 302 and want["staged_split2"] > 0 and want["to_fused"] == 2
+    assert 0 < rt["store_units"] <= (8192 << 20) // 16
+    # the named documents alone (a batch of more than 64): the same routes, document for document
+    sub = [docs[i] for i in named]
+    b1, o1 = gpu.pack(sub)
+    check(gpu, oracle, b1, o1, "staged, named documents")
+    r1 = gpu.last_route_stats(0).as_dict()
+    w1 = lrm.expected_routes(sub, [facts[i] for i in named], wide={0})
+    assert {f: r1[f] for f in lrm.FIELDS} == w1, (r1, w1)
+    assert (w1["long_list"], w1["staged_split1"] + w1["staged_whole"], w1["to_fused"]) == (404, 403, 2)
     env = dict(os.environ, CLD_LONG_STORE_MB="1",
                PYTHONPATH=os.pathsep.join(os.path.join(ROOT, p) for p in ("language-detector_amd", "oracle", "tests")))
     r = subprocess.run([sys.executable, "-c", STAGED], env=env, capture_output=True, text=True, timeout=110)

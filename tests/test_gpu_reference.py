@@ -116,6 +116,16 @@ def test_small_batches_speculate_and_equal_reference(gpu, ref):
         got = gpu.detect_batch(buf=b3, offsets=o3)
         st = gpu.last_stats(0)
         assert st.long_docs == n and st.general_docs == 0
+        # 64: the staged launches are skipped, the fused kernel takes the list whole; 600: stored and scored staged
+        rt = gpu.last_route_stats(0).as_dict()
+        staged = {f: rt[f] for f in ("staged_whole", "staged_split1", "groups1", "staged_pass2", "staged_split2",
+                                     "groups2", "to_fused", "store_units")}
+        assert rt["long_list"] == n
+        if n == 64:
+            assert not any(staged.values()), staged
+        else:
+            assert rt["staged_whole"] + rt["staged_split1"] + rt["to_fused"] >= n and rt["store_units"] > 0, rt
+            assert rt["staged_whole"] + rt["staged_split1"] > 0 and rt["staged_pass2"] > 0, rt
         assert st.passes[1] > n // 6 and st.passes[0] > 0    # both outcomes of the pass-1 wave occur (Q0: 44 / 556)
         same(got, ref.detect_batch(b3, o3, threads=16), "c3 %d" % n)
     for seed in (812, 813, 814):                         # ~1 MiB requests, each with ~180 long documents
