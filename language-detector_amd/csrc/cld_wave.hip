@@ -59,6 +59,16 @@ __device__ __forceinline__ uint64_t lanemask_lt(int lane) { return lane ? (~0ull
 __device__ __forceinline__ int below(uint64_t m) {
   return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
+// This lane's bit of a mask (the inverse of a ballot): the mask itself becomes
+// the condition of the select or exec-mask region that uses the result, with
+// no per-lane 64-bit shift.  m MUST be wave-uniform (a ballot, a readlane /
+// readfirstlane result, or scalar arithmetic on such): the hardware reads one
+// value for the wave, so a mask that differs between lanes gives lane 0's.
+// Combine masks first (a & b & ~c stay on the scalar unit), then ask once.
+__device__ __forceinline__ bool lane_bit(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+// The lanes below n as a mask, on scalars: the lanes of a window at w0 whose
+// position w0 + lane is below w0 + n.
+__device__ __forceinline__ uint64_t first_lanes(int n) { return n >= 64 ? ~0ull : n <= 0 ? 0ull : (1ull << n) - 1; }
 // The lane id recomputed where a stage starts (v_mbcnt, as volatile asm): the
 // compiler would otherwise hoist the per-lane values derived from it out of
 // the document's span loop and spill them to scratch (8 waves/SIMD leave 64
@@ -182,6 +192,7 @@ struct Smem {
   union alignas(16) {                 // stage-local arrays
     uint16_t nx[CAP];                 // load: p + ScanToLetterOrSpecial(p, L - p)
     uint32_t low[CAP];                // load -> first span: lowered character starting here (pack_lowered)
+    uint8_t qcls[C::LB];              // quad_hits' position pass only: quad_class of every text byte
     struct {                          // hit stages -> scoring: base emissions (offset, langprob) in
       uint32_t be_lp[C::NE];          // linear order, written by the lanes that probed (emit_base)
       uint16_t be_off[C::NE + 1];
@@ -323,7 +334,7 @@ __device__ bool load_document(const DevTables& T, const uint8_t* __restrict__ g,
       slow |= st == 3 ? 1 : 0;
       s.sn[p] = (uint8_t)e;
       s.a.low[p] = pack_lowered(e);
-      const uint64_t m = __ballot(st == 1 && (e & 0xFF) != 0);
+      const uint64_t m = __ballot(st == 1) & __ballot((uint8_t)e != 0);
       if (lane == 0) s.lsm[w] = m;                      // (a lane-indexed register array would live in scratch)
     }
     slow |= wsum(conts - need) != 0 ? 1 : 0;               // every continuation byte is claimed
@@ -400,6 +411,42 @@ __device__ bool stale_script_amp(const DevTables& T, Smem<CAP>& s, int L, const 
 }
 
 // ------------------------------------------------ stage 1: one script span
+// The events of window w of a span that starts at q, as wave-uniform masks
+// over the window's lanes: Lm the lead bytes of [q, L), Bm the characters the
+// letters loop breaks on, Om / Fm the letter stops of the span script (or
+// Inherited) / of another script; c is the lane's byte.  Every lane reads its
+// byte and script, lanes past L and continuation bytes included: x <= 255 and
+// the lookahead's xn = x + utf8_len <= 259, inside the DOC = 288 bytes of
+// s.doc (zero-padded) and s.sn (what it holds past L is masked by Lm before
+// any use).  The compares are the ballots, and the rest is
+// scalar: no exec-mask region, except that the lookahead past a letter of a
+// third script is made only in a window that has one (uniform).
+template <int CAP, bool PLAIN>
+__device__ __forceinline__ void span_events(const DevTables& T, const Smem<CAP>& s, int w, int q, int L, int lane,
+                                            int spanscript, uint32_t& c, uint64_t& validm, uint64_t& Lm, uint64_t& Bm,
+                                            uint64_t& Om, uint64_t& Fm) {
+  using C = Cfg<CAP>;
+  const int common = (int)T.common, inherited = (int)T.inherited;
+  const int x = w * 64 + lane;
+  const int lo = q - w * 64 > 0 ? q - w * 64 : 0, hi = L - w * 64;       // (hi >= 1: the window loops stop at L)
+  validm = (hi >= 64 ? ~0ull : (1ull << hi) - 1) & (~0ull << lo);
+  c = s.doc[x];
+  const int sc = s.sn[x];
+  Lm = validm & __ballot((c & 0xC0) != 0x80);
+  const uint64_t ownm = __ballot(sc == spanscript) | __ballot(sc == inherited), comm = __ballot(sc == common);
+  uint64_t lookm = 0;
+  if (Lm & ~ownm & ~comm) {
+    // (a lookahead onto a rewritten HTML entity sees the raw '&': script 0)
+    const int xn = x + utf8_len((uint8_t)c);
+    const int sc2 = (!PLAIN && xn < 64 * C::NM && ((s.ent[xn >> 6] >> (xn & 63)) & 1)) ? 0 : s.sn[xn];
+    lookm = ~(__ballot(sc2 == common) | __ballot(sc2 == spanscript));
+  }
+  Bm = Lm & ~ownm & (comm | lookm);
+  const uint64_t Sm = ufl64(s.lsm[w]);
+  Om = Lm & Sm & ownm;
+  Fm = Lm & Sm & ~ownm;
+}
+
 // GetOneScriptSpan (getonescriptspan.cc:799-1027, plain text) as runs:
 // ' ' + run1 + ' ' + run2 + ' ' ... + runK + ' ' + "   \0".  A run starts at
 // a letter stop of the span script (or Inherited) and ends at the first
@@ -410,7 +457,6 @@ template <int CAP, bool PLAIN>
 __device__ int next_span(const DevTables& T, Smem<CAP>& s, int L, int& next, int& ulscript, int lane) {
   lane = lane_here();
   using C = Cfg<CAP>;
-  const int common = (int)T.common, inherited = (int)T.inherited;
   const int q = find_first<C::NM>(s.lsm, next, L);
   if (q >= L) { next = L; return 0; }
   const int spanscript = ufl(s.sn[q]);
@@ -425,37 +471,18 @@ __device__ int next_span(const DevTables& T, Smem<CAP>& s, int L, int& next, int
   int put = 1, take = L;
   bool run = true;                                   // q is an O event
   for (int w = q >> 6; w < C::NM && w * 64 < L; ++w) {
-    const int x = w * 64 + lane;
-    const bool valid = x >= q && x < L;
-    const uint32_t c = valid ? s.doc[x] : 0u;
-    const bool lead = valid && (c & 0xC0) != 0x80;
-    bool brk = false, ok = false, foreign = false;
-    if (lead) {
-      const int sc = s.sn[x];
-      if (sc != spanscript && sc != inherited) {
-        if (sc == common) {
-          brk = true;
-        } else {
-          // (a lookahead onto a rewritten HTML entity sees the raw '&': script 0)
-          const int xn = x + utf8_len((uint8_t)c);
-          const int sc2 = (!PLAIN && xn < 64 * C::NM && ((s.ent[xn >> 6] >> (xn & 63)) & 1)) ? 0 : s.sn[xn];
-          brk = sc2 != common && sc2 != spanscript;
-        }
-      }
-      if ((s.lsm[w] >> lane) & 1) {
-        if (sc == spanscript || sc == inherited) ok = true;
-        else foreign = true;
-      }
-    }
-    const uint64_t Bm = __ballot(brk), Om = __ballot(ok);
+    uint32_t c;
+    uint64_t validm, Lm, Bm, Om, Fm;
+    span_events<CAP, PLAIN>(T, s, w, q, L, lane, spanscript, c, validm, Lm, Bm, Om, Fm);
     const uint64_t evm = Bm | Om;
     const uint64_t ev_le = evm & (lane == 63 ? ~0ull : ((2ull << lane) - 1)), ev_lt = evm & lanemask_lt(lane);
     const bool inrun = ev_le ? ((Om >> (63 - __builtin_clzll(ev_le))) & 1) : run;
     const bool prev_run = ev_lt ? ((Om >> (63 - __builtin_clzll(ev_lt))) & 1) : run;
-    const uint64_t Em = __ballot(foreign && (brk || !prev_run));   // F while in a gap: the span ends here
+    const uint64_t prevm = __ballot(prev_run);
+    const uint64_t Em = Fm & (Bm | ~prevm);                // F while in a gap: the span ends here
     const int stop = Em ? __builtin_ctzll(Em) : 64;
-    const bool cp = valid && inrun && lane < stop;
-    const bool sep = brk && prev_run && lane <= stop;
+    const bool cp = lane_bit(validm) && inrun && lane < stop;
+    const bool sep = lane_bit(Bm & prevm) && lane <= stop;
     const int cnt = (cp ? 1 : 0) + (sep ? 1 : 0);
     const int pos = put + excl_scan(cnt, lane);
     if (cp) s.sbuf[pos] = (uint8_t)c;
@@ -633,7 +660,6 @@ template <int CAP, bool PLAIN>
 __device__ int span_lowered(const DevTables& T, Smem<CAP>& s, int L, int& next, int& ulscript, int lane, bool lowv) {
   lane = lane_here();
   using C = Cfg<CAP>;
-  const int common = (int)T.common, inherited = (int)T.inherited;
   const int q = find_first<C::NM>(s.lsm, next, L);
   if (q >= L) { next = L; return 0; }
   const int spanscript = ufl(s.sn[q]);
@@ -666,36 +692,17 @@ __device__ int span_lowered(const DevTables& T, Smem<CAP>& s, int L, int& next, 
   uint32_t e0 = ev[0], e1 = ev[1], e2 = ev[2], e3 = ev[3];
   for (int i = q >> 6; i > 0; --i) { e0 = e1; e1 = e2; e2 = e3; }
   if (lane == 0) s.lbuf[0] = ' ';
-  int put = 1, take = L, bad = 0;
+  int put = 1, take = L;
+  bool bad = false;                                  // (uniform) a kept character the table cannot lower here
   bool run = true;                                   // q is an O event
   for (int w = q >> 6; w < C::NM && w * 64 < L; ++w) {
-    const int x = w * 64 + lane;
-    const bool valid = x >= q && x < L;
-    const uint32_t c = valid ? s.doc[x] : 0u;
-    const bool lead = valid && (c & 0xC0) != 0x80;
-    bool brk = false, ok = false, foreign = false;
-    if (lead) {
-      const int sc = s.sn[x];
-      if (sc != spanscript && sc != inherited) {
-        if (sc == common) {
-          brk = true;
-        } else {
-          // (a lookahead onto a rewritten HTML entity sees the raw '&': script 0)
-          const int xn = x + utf8_len((uint8_t)c);
-          const int sc2 = (!PLAIN && xn < 64 * C::NM && ((s.ent[xn >> 6] >> (xn & 63)) & 1)) ? 0 : s.sn[xn];
-          brk = sc2 != common && sc2 != spanscript;
-        }
-      }
-      if ((s.lsm[w] >> lane) & 1) {
-        if (sc == spanscript || sc == inherited) ok = true;
-        else foreign = true;
-      }
-    }
+    uint32_t c;
+    uint64_t validm, Lm, Bm, Om, Fm;
+    span_events<CAP, PLAIN>(T, s, w, q, L, lane, spanscript, c, validm, Lm, Bm, Om, Fm);
     // next_span's inrun / prev_run on wave-uniform masks: the state after
     // position i is O_i | (!event_i & state_{i-1}), the carry recurrence of an
     // adder with generate O and propagate ~events -- so the carries into each
     // bit of (O | ~events) + O + run are prev_run, and one step more inrun.
-    const uint64_t Bm = __ballot(brk), Om = __ballot(ok), Fm = __ballot(foreign), Lm = __ballot(lead);
     const uint64_t evm = Bm | Om;
     const uint64_t ca = Om | ~evm;
     const uint64_t prevm = (ca + Om + (run ? 1ull : 0ull)) ^ ca ^ Om;
@@ -703,17 +710,24 @@ __device__ int span_lowered(const DevTables& T, Smem<CAP>& s, int L, int& next, 
     const uint64_t Em = Fm & (Bm | ~prevm);            // F while in a gap: the span ends here
     const int stop = Em ? __builtin_ctzll(Em) : 64;
     const uint64_t lt_stop = Em ? (Em & (0 - Em)) - 1 : ~0ull, le_stop = Em ? (Em ^ (Em - 1)) : ~0ull;
-    const bool cl = ((Lm & runm & lt_stop) >> lane) & 1;    // a kept character: its lowered bytes
-    const bool sep = ((Bm & prevm & le_stop) >> lane) & 1;  // (never both: a B event ends the run)
+    const uint64_t clm = Lm & runm & lt_stop;           // the kept characters: their lowered bytes
+    const uint64_t sepm = Bm & prevm & le_stop;         // (never both: a B event ends the run)
     const uint32_t e = e0;
-    const bool low = e != 0xFFFFFFFFu;
-    bad |= (cl && !low) ? 1 : 0;
-    const int olen = sep ? 1 : (cl && low) ? (int)(e >> 24) : 0;
+    const uint64_t lowm = __ballot(e != 0xFFFFFFFFu);
+    bad |= (clm & ~lowm) != 0;
+    const bool sep = lane_bit(sepm);
+    const int olen = sep ? 1 : lane_bit(clm & lowm) ? (int)(e >> 24) : 0;
     const uint32_t o = sep ? (uint32_t)' ' : e;
     const int pos = put + excl_scan(olen, lane);
     put = rdl(pos + olen, 63);
-    if (put + 8 > C::LB - 16) { bad = 1; break; }      // (uniform; lower_span's LB check, closing bytes included)
-    for (int k = 0; k < olen; ++k) s.lbuf[pos + k] = (uint8_t)(o >> (8 * k));
+    if (put + 8 > C::LB - 16) { bad = true; break; }   // (uniform; lower_span's LB check, closing bytes included)
+    if (olen > 0) {                                     // (olen <= 3: pack_lowered)
+      s.lbuf[pos] = (uint8_t)o;
+      if (olen > 1) {
+        s.lbuf[pos + 1] = (uint8_t)(o >> 8);
+        if (olen > 2) s.lbuf[pos + 2] = (uint8_t)(o >> 16);
+      }
+    }
     if (stop < 64) {
       take = w * 64 + stop;
       run = false;
@@ -722,7 +736,7 @@ __device__ int span_lowered(const DevTables& T, Smem<CAP>& s, int L, int& next, 
     run = (runm >> 63) != 0;
     e0 = e1; e1 = e2; e2 = e3;
   }
-  if (__ballot(bad != 0)) {
+  if (bad) {
     const int tb = next_span<CAP, PLAIN>(T, s, L, next, ulscript, lane);
     return lower_span<CAP>(T, s, tb, lane);
   }
@@ -760,6 +774,20 @@ __device__ __forceinline__ uint32_t quad_hash_lds(const uint8_t* text, int p, in
 }
 
 // ------------------------------------------------ stage 3: hit streams
+// What GetQuadHits' step (cldutil.cc:340-400) asks of a text byte, one value
+// per byte: bits 0-2 adv_but_space (0 for a space or control byte, else the
+// UTF-8 length its lead bits give, 1 for a continuation byte), bit 3
+// adv_space_vowel (space or control, continuation byte, ASCII vowel), bit 4
+// the byte is ' '.
+__device__ __forceinline__ uint32_t quad_class(uint32_t c) {
+  constexpr uint32_t kVowels = 1u << 1 | 1u << 5 | 1u << 9 | 1u << 15 | 1u << 21;   // AEIOU / aeiou by c & 31
+  const int ones = __builtin_clz(~(c << 24));            // leading one bits of the byte
+  const bool low = c <= 0x20;
+  const uint32_t adv = low ? 0u : (uint32_t)min(max(ones, 1), 4);
+  const bool sv = low || ones == 1 || ((c & 0xC0) == 0x40 && ((kVowels >> (c & 31)) & 1));
+  return adv | (sv ? 8u : 0u) | (c == ' ' ? 16u : 0u);
+}
+
 // Base hits -> base emissions, by the lanes that probed (the first half of
 // LinearizeAll, scoreonescriptspan.cc:856-911): a kept hit's one or two
 // langprobs, zeros dropped, appended in hit order to s.a.e.  Called by all 64
@@ -821,27 +849,42 @@ __device__ int quad_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, i
   const int last = start < limit ? limit : start;      // the end offset (below)
   int nws = start < limit ? 1 : 0;
   nw = 0;
+  // A byte's part in a step does not depend on which position asks: every
+  // lane classifies its own byte once (quad_class), and the four hops of a
+  // step are "read class, add".  A step from p <= last reads at most 16
+  // bytes on, and what it finds past `last` is the padding ("  " and NULs:
+  // advance 0), which is classified like the text, so a step sees what it saw
+  // when it read the text itself whatever the span's last bytes are; the
+  // lanes past the padding redo start's (last + kQuadPad < LB: the span
+  // passes keep 23 bytes of padding inside lbuf).
+  constexpr int kQuadPad = 22;
+  uint8_t* cls = s.a.qcls;
+  for (int w0 = start; w0 <= last + kQuadPad; w0 += 64) {
+    const int pc = lane_bit(first_lanes(last + kQuadPad - w0 + 1)) ? w0 + lane : start;
+    cls[pc] = (uint8_t)quad_class(text[pc]);
+  }
+  wsync();
   for (int w0 = start; w0 <= last; w0 += 64) {
     const int p = w0 + lane;
-    const bool in = p < limit;
-    const int pc = p <= last ? p : start;
-    const uint32_t c0 = text[pc];
-    const int a1 = pc + adv_but_space((uint8_t)c0);
-    const int a2 = a1 + adv_but_space(text[a1]);
-    const uint32_t c2 = text[a2];
-    const int a3 = a2 + adv_but_space((uint8_t)c2);
-    const int a4 = a3 + adv_but_space(text[a3]);
-    const int nx = a2 + adv_space_vowel((uint8_t)c2);
-    const bool fin = text[a4] == ' ' || a2 >= limit || nx >= limit;
-    if (in) nfo[p] = (uint16_t)((a4 - p) | ((nx - p) << 5) | (fin ? 0x400 : 0));
-    const bool sp = p <= last && c0 == ' ';
-    const uint64_t m = __ballot(sp);
-    if (sp) {
-      const int k = nw + below(m);
+    // (p <= last, p < limit: lane ranges, made on scalars)
+    const uint64_t lastm = first_lanes(last - w0 + 1), inm = first_lanes(limit - w0);
+    const int pc = lane_bit(lastm) ? p : start;
+    const uint32_t k0 = cls[pc];
+    const int a1 = pc + (int)(k0 & 7);
+    const int a2 = a1 + (cls[a1] & 7);
+    const uint32_t k2 = cls[a2];
+    const int a3 = a2 + (int)(k2 & 7);
+    const int a4 = a3 + (cls[a3] & 7);
+    const int nx = a2 + (int)((k2 >> 3) & 1);
+    const uint64_t spm = lastm & __ballot(k0 >= 16);          // (bit 4 is the top one)
+    const uint64_t finm = __ballot(cls[a4] >= 16) | __ballot(a2 >= limit) | __ballot(nx >= limit);
+    if (lane_bit(inm)) nfo[p] = (uint16_t)((a4 - p) | ((nx - p) << 5) | (lane_bit(finm) ? 0x400 : 0));
+    if (lane_bit(spm)) {
+      const int k = nw + below(spm);
       if (k <= C::NB) s.wsp[k] = (uint16_t)p;
     }
-    nw += __popcll(m);
-    nws += __popcll(__ballot(sp && p < limit - 1));    // (a word start follows)
+    nw += __popcll(spm);
+    nws += __popcll(spm & first_lanes(limit - 1 - w0));    // (p < limit - 1: a word start follows)
   }
   if (nws > C::NB || nw > C::NB) return -1;
   if (lane < C::QM) s.qmark[lane] = 0u;
@@ -864,7 +907,7 @@ __device__ int quad_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, i
   int n = 0;
   for (int w = start >> 6; w * 64 < limit; ++w) {
     const uint64_t m = ufl64(*reinterpret_cast<const uint64_t*>(&s.qmark[2 * w]));
-    if ((m >> lane) & 1) {
+    if (lane_bit(m)) {
       const int k = n + below(m);
       if (k < C::NB) s.qchn[k] = (uint16_t)(w * 64 + lane);
     }
@@ -905,7 +948,7 @@ __device__ int quad_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, i
     const uint32_t h2 = (uint32_t)__shfl((int)hv, q2 < 0 ? lane : q2, 64);
     const uint32_t a = q1 < 0 ? A : h1;
     const uint32_t b = q1 < 0 ? B : (q2 < 0 ? A : h2);
-    const uint64_t cm = __ballot(hit && (hv == a || hv == b));
+    const uint64_t cm = hm & (__ballot(hv == a) | __ballot(hv == b));
     uint64_t k = hm;
     if (cm) {
       const int f = __builtin_ctzll(cm);
@@ -927,7 +970,7 @@ __device__ int quad_hits(const DevTables& T, Smem<CAP>& s, int limit, int& nb, i
       B = r2 ? rdlu(hv, 63 - __builtin_clzll(r2)) : A;
       A = rdlu(hv, t1);
     }
-    if (!emit_base<CAP>(s, T.quad, T.quad2, (k >> lane) & 1, pr, p, eb)) return -1;
+    if (!emit_base<CAP>(s, T.quad, T.quad2, lane_bit(k), pr, p, eb)) return -1;
     base += __popcll(k);
   }
   nb = base;
@@ -991,7 +1034,7 @@ __device__ bool octa_hits(const DevTables& T, Smem<CAP>& s, int start, int nw, i
     const uint64_t h1 = wshr1_64(w), h2 = wshr1_64(h1);   // lanes - 1, - 2 (used from lanes 1, 2 on)
     const uint64_t pa = lane >= 1 ? h1 : A;
     const uint64_t pb = lane >= 2 ? h2 : (lane == 1 ? A : B);
-    const uint64_t cm = __ballot(v && (w == pa || w == pb));
+    const uint64_t cm = vm & (__ballot(w == pa) | __ballot(w == pb));
     uint64_t k = vm;
     uint64_t tp = pa;
     if (cm) {
@@ -1023,7 +1066,7 @@ __device__ bool octa_hits(const DevTables& T, Smem<CAP>& s, int start, int nw, i
   for (int r = 0; r < C::NR; ++r) {
     if (r * 64 >= nw) break;
     uint32_t pp = 0, xp = 0, dp = 0;
-    const bool k = (keep[r] >> lane) & 1;
+    const bool k = lane_bit(keep[r]);
     if (k) {
       const uint64_t tph = ((uint64_t)thi[r] << 32) | tlo[r];
       if (tph != 0 && tph != wh[r]) pp = octa_lookup<true>(T.distinctocta, pair_hash(tph, wh[r]));
@@ -1342,7 +1385,7 @@ __device__ bool score_round(const DevTables& T, Smem<CAP>& s, int ulscript, bool
     // sorts three (CurrentTopThreeKeys) but SetChunkSummary reads only the
     // first two (scoreonescriptspan.cc:60-96), so two rounds.
     const uint2 v2 = reinterpret_cast<const uint2*>(s.tote)[lane];
-    const bool inuse = (gm >> lane) & 1;
+    const bool inuse = lane_bit(gm);
     uint32_t cand[4] = {v2.x & 0xFFFF, v2.x >> 16, v2.y & 0xFFFF, v2.y >> 16};
     int key3[2] = {-1, -1};
     uint32_t sc3[2] = {0, 0};
@@ -1464,7 +1507,7 @@ __device__ __forceinline__ void sort3_regs(SlotRegs& r, int lane) {
     if (R) {
       const uint64_t below = R & lanemask_lt(lane);
       const int src = lane == p ? 63 - __builtin_clzll(R)
-                    : ((R >> lane) & 1) ? (below ? 63 - __builtin_clzll(below) : p) : lane;
+                    : lane_bit(R) ? (below ? 63 - __builtin_clzll(below) : p) : lane;
       r.key = (uint32_t)__shfl((int)r.key, src, 64);
       r.val = __shfl(r.val, src, 64);
       r.sc = __shfl(r.sc, src, 64);
