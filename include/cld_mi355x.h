@@ -605,6 +605,87 @@ int cld_detect_batch_device_vec_docflags(int device, const uint8_t* d_buf, const
                                          uint64_t* d_chunk_offsets, int32_t* d_valid_prefix, cld_vec_status* d_status,
                                          void* stream);
 
+/* A batch split by the language of its chunks: per-language totals over the
+ * chunk vectors of a batch, and the pieces in chosen languages packed into a
+ * new batch -- "which part of the text is in which language"
+ * (compact_lang_det.h:147-153) acted on without leaving the GPU.
+ *
+ * The batch is buf, offsets[0..n]; its vectors are chunks, chunk_offsets[0..n]
+ * as cld_detect_batch_vec / cld_detect_batch_device_vec write them, and
+ * chunk_cap is the number of entries chunks really holds.
+ *   document i   has len = offsets[i + 1] - offsets[i] bytes, 0 if that is
+ *                negative, and the vector chunks[chunk_offsets[i] ..
+ *                min(chunk_offsets[i + 1], chunk_cap)), empty if that range is
+ *                empty or inverted.  Chunks at or past chunk_cap do not exist
+ *                (the CLD_ENOSPC case of the vector entries: the offsets hold the
+ *                true totals, memory the first chunk_cap chunks).
+ *   the piece    of a chunk is the byte range [s, e) of its document, s =
+ *                clamp(offset, 0, len), e = clamp((int64)offset + bytes, s, len).
+ *                Negative bytes, offsets outside the document, overlapping and
+ *                repeated chunks are legal input: no chunk word makes an entry
+ *                read a byte outside [offsets[i], offsets[i + 1]) or write
+ *                outside its output.
+ *   the bin      of a chunk is min(lang1, CLD_NUM_LANGUAGES), the CLD_GROUP_BINS
+ *                bins of the group entries.
+ * cld_chunk_totals (the host reference, no GPU) / cld_chunk_totals_device:
+ *   chunk_counts[CLD_GROUP_BINS]  (NULL: not wanted) the chunks per bin; every
+ *                                 existing chunk counts, an empty piece too
+ *   chunk_bytes[CLD_GROUP_BINS]   (NULL: not wanted) the sum of e - s per bin
+ * cld_gather_chunks (the host reference, no GPU) / cld_gather_chunks_device:
+ *   select[CLD_GROUP_BINS]        one byte per bin, nonzero: keep
+ *   output document i is the concatenation, in vector order, of the pieces of
+ *   document i whose bin is selected and which are not empty (the kept pieces);
+ *   the output batch has n documents, many of them possibly empty.  With
+ *   CLD_CHUNKS_SPACE a kept piece is preceded by one 0x20 unless its chunk is
+ *   the first of its document's vector, or the chunk before it in the vector
+ *   is itself a kept piece that ends exactly where this one starts: words are
+ *   not glued across a removed stretch, and a leading space is harmless to the
+ *   detector.  Any other flag bit: CLD_EINVAL.  With flags == 0 and one
+ *   selected bin L the output holds chunk_bytes[L] bytes: the totals size
+ *   out_buf exactly.
+ *   out_offsets[0..n] is always the exclusive prefix sum of the true output
+ *   lengths; out_buf[0, min(out_offsets[n], out_cap)) receives the bytes and
+ *   nothing at or past out_buf + out_cap is written (out_cap == 0 with out_buf
+ *   NULL: the sizing pass).  The output must not overlap buf.  It is a batch
+ *   for every cld_detect_batch_device* entry, buf_bytes = out_offsets[n].
+ * The device entries: every pointer in device memory of GPU `device` (8-byte
+ * aligned where it holds 64-bit words, 4-byte aligned chunks), enqueued on
+ * `stream` (NULL: the runtime's); asynchronous, the host waits for nothing and
+ * reads no device word; none of the context's scratch is used.  d_work holds
+ * work_bytes >= cld_chunk_work_bytes(n, chunk_cap) bytes (a smaller one:
+ * CLD_ENOSPC, nothing enqueued) and is free again when the call's work on the
+ * stream is done.  cld_chunk_work_bytes is 8 * (chunk_cap + 1) bytes -- the
+ * output position of every chunk's piece -- plus a fixed 2.4 MB (the totals'
+ * per-range counts and bytes over the bins; the scans' per-range sums); n does
+ * not enter.  The output is the same from run to run: no atomic decides a
+ * position or a byte.  Inputs are only read.
+ * chunk_offsets may be anything; vectors of two documents overlap only where
+ * it goes down and up again.  cld_gather_chunks_device holds one position per
+ * chunk, so where overlapping vectors hold more than chunk_cap (or
+ * CLD_CHUNKS_MAX) chunks together it takes the first chunk_cap of them in
+ * document order and the rest do not exist; the other three entries take them
+ * all.
+ * CLD_EINVAL: n > INT32_MAX, chunk_cap > UINT32_MAX, NULL chunk_offsets, NULL
+ * select, out_cap > 0 with NULL out_buf, and with n > 0 a NULL offsets,
+ * out_offsets or workspace, NULL chunks with chunk_cap > 0, or NULL buf with
+ * out_cap > 0.  n == 0: CLD_OK, with zero totals and out_offsets[0] = 0 written
+ * where those pointers are not NULL. */
+#define CLD_CHUNKS_SPACE 1u             /* one 0x20 before a kept piece that does not continue the one before it */
+#define CLD_CHUNKS_MAX 0xFFF00000ull    /* chunks one cld_gather_chunks_device call can place */
+size_t cld_chunk_work_bytes(size_t n, uint64_t chunk_cap);
+int cld_chunk_totals(const uint64_t* offsets, size_t n, const cld_chunk* chunks, uint64_t chunk_cap,
+                     const uint64_t* chunk_offsets, uint64_t* chunk_counts, uint64_t* chunk_bytes);
+int cld_chunk_totals_device(int device, const uint64_t* d_offsets, size_t n, const cld_chunk* d_chunks,
+                            uint64_t chunk_cap, const uint64_t* d_chunk_offsets, uint64_t* d_chunk_counts,
+                            uint64_t* d_chunk_bytes, void* d_work, size_t work_bytes, void* stream);
+int cld_gather_chunks(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_chunk* chunks,
+                      uint64_t chunk_cap, const uint64_t* chunk_offsets, const uint8_t* select, uint32_t flags,
+                      uint8_t* out_buf, uint64_t out_cap, uint64_t* out_offsets);
+int cld_gather_chunks_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                             const cld_chunk* d_chunks, uint64_t chunk_cap, const uint64_t* d_chunk_offsets,
+                             const uint8_t* d_select, uint32_t flags, uint8_t* d_out_buf, uint64_t out_cap,
+                             uint64_t* d_out_offsets, void* d_work, size_t work_bytes, void* stream);
+
 /* The preparation step alone, on GPU 0 (host buffers): out_buf receives the
  * prepared documents back to back (capacity >= offsets[n]-offsets[0] + n
  * bytes), out_offsets[0..n] their offsets.  flags: CLD_FLAG_STRIP_EXTRAS and/or

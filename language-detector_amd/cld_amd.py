@@ -16,6 +16,9 @@ Mirrors the reference's caller-facing interface for this path:
   group_by_language(results)              counts, stable order and group offsets per language (host reference)
   group_by_language_device / gather_docs_device   the same over results in HBM, and the chosen
                                           documents packed into a new device batch
+  chunk_totals / gather_chunks            per-language totals over chunk vectors, and the pieces in chosen
+                                          languages packed into a new batch (host references)
+  chunk_totals_device / gather_chunks_device      the same over a batch and its vectors in HBM
   detect_language_scrubbed(text)          the repair on the host, then detect_language
 There is no CPU fallback: if the HIP library or a GPU is missing, calls raise.
 """
@@ -50,6 +53,7 @@ GROUP_TOP1 = 1             # include/cld_mi355x.h CLD_GROUP_TOP1: the key is lan
 GROUP_RELIABLE_ONLY = 2    # include/cld_mi355x.h CLD_GROUP_RELIABLE_ONLY: unreliable documents get key UNKNOWN_LANGUAGE
 GROUP_WGS = 256            # csrc/cld_kernels.h kGroupWgs: the group entries cut a batch into at most this many ranges
 GROUP_TILE = 512           # csrc/cld_kernels.h kGroupTile: documents per step of a range's workgroup
+CHUNKS_SPACE = 1           # include/cld_mi355x.h CLD_CHUNKS_SPACE: a 0x20 before a kept piece that does not continue the one before
 
 RESULT_DTYPE = np.dtype([("lang3", "<u2", 3), ("summary_lang", "<u2"), ("percent3", "i1", 3),
                          ("is_reliable", "u1"), ("text_bytes", "<i4"), ("normalized3", "<f8", 3)])
@@ -69,7 +73,8 @@ EXPORTS = ("detect_language", "cld_init", "cld_init_device", "cld_shutdown", "cl
            "cld_detect_batch_vec_docflags", "cld_detect_batch_device_docflags",
            "cld_detect_batch_device_vec_docflags", "cld_scrub_utf8_host", "cld_scrub_utf8_batch",
            "cld_scrub_utf8_device", "detect_language_scrubbed", "cld_group_work_bytes", "cld_group_by_language",
-           "cld_group_by_language_device", "cld_gather_docs_device", "cld_last_route_stats")
+           "cld_group_by_language_device", "cld_gather_docs_device", "cld_last_route_stats", "cld_chunk_work_bytes",
+           "cld_chunk_totals", "cld_chunk_totals_device", "cld_gather_chunks", "cld_gather_chunks_device")
 CHUNK_DTYPE = np.dtype([("offset", "<i4"), ("bytes", "<i4"), ("lang1", "<u2"), ("pad", "<u2")])   # cld_chunk
 
 
@@ -237,6 +242,12 @@ def lib():
         L.cld_group_by_language.argtypes = [vp, sz, u32, vp, vp, vp, vp, vp]
         L.cld_group_by_language_device.argtypes = [ctypes.c_int, vp, sz, u32, vp, vp, vp, vp, vp, vp, sz, vp]
         L.cld_gather_docs_device.argtypes = [ctypes.c_int, vp, vp, sz, vp, sz, vp, u64, vp, vp, sz, vp]
+        L.cld_chunk_work_bytes.argtypes = [sz, u64]
+        L.cld_chunk_work_bytes.restype = sz
+        L.cld_chunk_totals.argtypes = [vp, sz, vp, u64, vp, vp, vp]
+        L.cld_chunk_totals_device.argtypes = [ctypes.c_int, vp, sz, vp, u64, vp, vp, vp, vp, sz, vp]
+        L.cld_gather_chunks.argtypes = [vp, vp, sz, vp, u64, vp, vp, u32, vp, u64, vp]
+        L.cld_gather_chunks_device.argtypes = [ctypes.c_int, vp, vp, sz, vp, u64, vp, vp, u32, vp, u64, vp, vp, sz, vp]
         _lib = L
     return _lib
 
@@ -733,6 +744,87 @@ def gather_docs_device(device, d_buf_ptr, d_offsets_ptr, n_src, d_index_ptr, m, 
                                       d_out_offsets_ptr, d_work_ptr, work_bytes, stream_ptr)
     if rc != 0:
         raise CldError("cld_gather_docs_device failed: %d" % rc)
+
+
+def chunk_work_bytes(n, chunk_cap):
+    """cld_chunk_work_bytes: the workspace either chunk device entry needs: 8 * (chunk_cap + 1) bytes and a fixed part."""
+    return int(lib().cld_chunk_work_bytes(n, chunk_cap))
+
+
+def _chunk_args(offsets, chunks, chunk_offsets, chunk_cap):
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    chunk_offsets = np.ascontiguousarray(chunk_offsets, dtype=np.uint64)
+    chunks = np.ascontiguousarray(chunks, dtype=CHUNK_DTYPE)
+    if len(offsets) < 1 or len(chunk_offsets) != len(offsets):
+        raise ValueError("need n + 1 offsets and n + 1 chunk offsets")
+    cap = len(chunks) if chunk_cap is None else int(chunk_cap)
+    if cap > len(chunks):
+        raise ValueError("chunk_cap is more than the chunks given")
+    return offsets, chunks, chunk_offsets, cap
+
+
+def chunk_totals(offsets, chunks, chunk_offsets, chunk_cap=None):
+    """cld_chunk_totals (the host reference, no GPU) over a batch's offsets and its vectors (a CHUNK_DTYPE
+    array and chunk_offsets, as detect_batch_vec returns them; chunk_cap: the chunks that exist, default
+    all given) -> dict of chunk_counts and chunk_bytes, uint64[GROUP_BINS] each."""
+    offsets, chunks, chunk_offsets, cap = _chunk_args(offsets, chunks, chunk_offsets, chunk_cap)
+    got = {"chunk_counts": np.zeros(GROUP_BINS, np.uint64), "chunk_bytes": np.zeros(GROUP_BINS, np.uint64)}
+    rc = lib().cld_chunk_totals(offsets.ctypes.data, len(offsets) - 1, chunks.ctypes.data, cap, chunk_offsets.ctypes.data,
+                                got["chunk_counts"].ctypes.data, got["chunk_bytes"].ctypes.data)
+    if rc != 0:
+        raise CldError("cld_chunk_totals failed: %d" % rc)
+    return got
+
+
+def gather_chunks(buf, offsets, chunks, chunk_offsets, select, flags=0, chunk_cap=None, out_cap=None):
+    """cld_gather_chunks (the host reference, no GPU): the pieces of every document whose bin is set in
+    select (GROUP_BINS bytes, nonzero: keep) packed into a new batch -> (buffer, offsets uint64[n + 1]).
+    flags: CHUNKS_SPACE.  out_cap: the buffer's size (default: the sizing pass first, then all of it);
+    the offsets are the true totals either way."""
+    offsets, chunks, chunk_offsets, cap = _chunk_args(offsets, chunks, chunk_offsets, chunk_cap)
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    select = np.ascontiguousarray(select, dtype=np.uint8)
+    if len(select) != GROUP_BINS:
+        raise ValueError("select holds one byte per bin")
+    n = len(offsets) - 1
+    out_offsets = np.zeros(n + 1, np.uint64)
+
+    def call(out, out_bytes):
+        rc = lib().cld_gather_chunks(buf.ctypes.data, offsets.ctypes.data, n, chunks.ctypes.data, cap,
+                                     chunk_offsets.ctypes.data, select.ctypes.data, flags,
+                                     out.ctypes.data if out_bytes else None, out_bytes, out_offsets.ctypes.data)
+        if rc != 0:
+            raise CldError("cld_gather_chunks failed: %d" % rc)
+
+    if out_cap is None:
+        call(None, 0)
+        out_cap = int(out_offsets[n])
+    out = np.zeros(out_cap, np.uint8)
+    call(out, out_cap)
+    return out[:min(out_cap, int(out_offsets[n]))], out_offsets
+
+
+def chunk_totals_device(device, d_offsets_ptr, n, d_chunks_ptr, chunk_cap, d_chunk_offsets_ptr, d_work_ptr, work_bytes,
+                        d_chunk_counts_ptr=None, d_chunk_bytes_ptr=None, stream_ptr=None):
+    """cld_chunk_totals_device: every pointer in device memory (the batch's offsets, cld_chunk[chunk_cap],
+    chunk_offsets uint64[n + 1], counts / bytes uint64[GROUP_BINS], a workspace of
+    chunk_work_bytes(n, chunk_cap)); asynchronous on the stream."""
+    rc = lib().cld_chunk_totals_device(device, d_offsets_ptr, n, d_chunks_ptr, chunk_cap, d_chunk_offsets_ptr,
+                                       d_chunk_counts_ptr, d_chunk_bytes_ptr, d_work_ptr, work_bytes, stream_ptr)
+    if rc != 0:
+        raise CldError("cld_chunk_totals_device failed: %d" % rc)
+
+
+def gather_chunks_device(device, d_buf_ptr, d_offsets_ptr, n, d_chunks_ptr, chunk_cap, d_chunk_offsets_ptr, d_select_ptr,
+                         d_out_buf_ptr, out_cap, d_out_offsets_ptr, d_work_ptr, work_bytes, flags=0, stream_ptr=None):
+    """cld_gather_chunks_device: the pieces in the selected bins (d_select: GROUP_BINS bytes) of the device
+    batch packed into (d_out_buf, d_out_offsets uint64[n + 1]); out_cap 0 with no buffer sizes the output.
+    flags: CHUNKS_SPACE.  A workspace of chunk_work_bytes(n, chunk_cap); asynchronous on the stream."""
+    rc = lib().cld_gather_chunks_device(device, d_buf_ptr, d_offsets_ptr, n, d_chunks_ptr, chunk_cap,
+                                        d_chunk_offsets_ptr, d_select_ptr, flags, d_out_buf_ptr, out_cap,
+                                        d_out_offsets_ptr, d_work_ptr, work_bytes, stream_ptr)
+    if rc != 0:
+        raise CldError("cld_gather_chunks_device failed: %d" % rc)
 
 
 def valid_prefix_host(doc):

@@ -38,9 +38,13 @@
 #include <stdint.h>
 
 #include "cld_kernels.h"
+#include "cld_wgscan.h"
 
 namespace cld {
 namespace group {
+
+using wg::block_incl_scan;
+using wg::wave_find;
 
 constexpr int kBins = (int)CLD_GROUP_BINS;
 constexpr int kTile = kGroupTile;          // documents per step = threads per workgroup
@@ -55,24 +59,6 @@ constexpr int kCopyWgs = 2048;
 static_assert(kBins <= 1024, "peers() compares 10 key bits");
 static_assert(kBins <= 2 * kTile, "k_group_scatter scans two bins per thread");
 static_assert(kGroupWgs % 64 == 0 && kGroupWgs <= kTile, "k_group_scan / k_gather_scan read the ranges at once");
-
-// Inclusive scan over the workgroup's W waves (sm: W entries; safe to call again at once).
-template <typename T, int W>
-__device__ __forceinline__ T block_incl_scan(T v, T* sm) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T y = __shfl_up(v, d, 64);
-    if (lane >= d) v += y;
-  }
-  __syncthreads();                          // (an earlier call's sm has been read)
-  if (lane == 63) sm[w] = v;
-  __syncthreads();
-  T before = 0;
-#pragma unroll
-  for (int k = 0; k < W; ++k) before += k < w ? sm[k] : 0;
-  return v + before;
-}
 
 // The bin of document i: min(key, CLD_NUM_LANGUAGES).  flags is the same for every lane.
 __device__ __forceinline__ uint32_t doc_bin(const cld_result* __restrict__ res, uint32_t i, uint32_t flags) {
@@ -256,19 +242,6 @@ __global__ __launch_bounds__(kTile) void k_gather_scan(uint32_t m, uint32_t rang
     __syncthreads();
   }
   if (hi == m && tid == 0) out_offs[m] = carry;
-}
-
-// The largest j in [lo, hi) with off[j] <= p, given off[lo] <= p < off[hi]; the whole wave, 64 probes a step.
-__device__ __forceinline__ uint32_t wave_find(const uint64_t* __restrict__ off, uint32_t lo, uint32_t hi, uint64_t p,
-                                              int lane) {
-  while (hi - lo > 1) {
-    const uint32_t step = (hi - lo + 63) / 64;
-    const uint64_t q = lo + (uint64_t)(lane + 1) * step;
-    const bool le = q < hi && off[q] <= p;
-    lo += (uint32_t)__popcll(__ballot(le)) * step;       // (off does not decrease: the lanes that hold are the first ones)
-    hi = min(hi, lo + step);
-  }
-  return lo;
 }
 
 // Output bytes [c0, c1) of one lane, at most 16 and 16-byte aligned when 16; their documents lie in [j0, j1].

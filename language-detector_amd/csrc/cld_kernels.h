@@ -228,6 +228,26 @@ hipError_t cld_launch_group(const cld_result* res, uint32_t n, uint32_t flags, c
                             uint64_t* bin_bytes, uint32_t* order, uint64_t* group_offsets, void* work, hipStream_t s);
 hipError_t cld_launch_gather(const uint8_t* buf, const uint64_t* offs, uint32_t n_src, const uint32_t* index, uint32_t m,
                              uint8_t* out, uint64_t cap, uint64_t* out_offs, void* work, hipStream_t s);
+// cld_chunk_totals_device / cld_gather_chunks_device (cld_chunks.hip).  `work`
+// (cld_chunk_work(chunk_cap) bytes, 8-byte aligned, not zeroed): a fixed part
+// -- the totals' per-range counts and bytes over the bins, u64 each, for the
+// at most kGroupWgs ranges of cld_chunk_doc_range(n) documents; the gather's
+// instance count and per-range sums -- then chunk_cap + 1 u64, the gather's
+// output position of every chunk's piece.  n <= INT32_MAX, chunk_cap <=
+// UINT32_MAX.  cld_launch_chunk_totals: counts, bytes each nullable.
+// cld_launch_chunk_gather: out_offs[0..n] always, out[0, min(total, cap)) when
+// cap > 0.
+constexpr size_t kChunkWorkFixed = (size_t)kGroupWgs * 2 * CLD_GROUP_BINS * sizeof(uint64_t);
+inline size_t cld_chunk_work(uint64_t chunk_cap) { return kChunkWorkFixed + (size_t)(chunk_cap + 1) * sizeof(uint64_t); }
+inline uint32_t cld_chunk_doc_range(uint32_t n) {
+  const uint32_t per = n / kGroupWgs + (n % kGroupWgs != 0);
+  return per ? per : 1;
+}
+hipError_t cld_launch_chunk_totals(const uint64_t* offs, uint32_t n, const cld_chunk* chunks, const uint64_t* chunk_offs,
+                                   uint64_t chunk_cap, uint64_t* counts, uint64_t* bytes, void* work, hipStream_t s);
+hipError_t cld_launch_chunk_gather(const uint8_t* buf, const uint64_t* offs, uint32_t n, const cld_chunk* chunks,
+                                   const uint64_t* chunk_offs, uint64_t chunk_cap, const uint8_t* select, uint32_t flags,
+                                   uint8_t* out, uint64_t out_cap, uint64_t* out_offs, void* work, hipStream_t s);
 // ApplyHints (cld_hints.hip; compact_lang_det_impl.cc:1587-1684), one wave
 // per document: priors14 (14 per document, trimmed to 4, zero-padded),
 // boosts16 (the 16 langprobs enqueue() takes as `priors`) and special (the

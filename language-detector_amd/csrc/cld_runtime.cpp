@@ -2710,6 +2710,134 @@ int cld_gather_docs_device(int device, const uint8_t* d_buf, const uint64_t* d_o
   return CLD_OK;
 }
 
+size_t cld_chunk_work_bytes(size_t n, uint64_t chunk_cap) {
+  (void)n;   // a fixed number of workgroup ranges whatever n is; one position per chunk (cld_kernels.h)
+  return cld_chunk_work(chunk_cap);
+}
+
+// The host references of the chunk entries, written from the definitions in cld_mi355x.h.
+namespace {
+struct HostPiece {
+  int64_t s, e;
+  uint32_t bin;
+};
+HostPiece host_piece(const cld_chunk& c, int64_t len) {
+  HostPiece p;
+  p.s = std::min<int64_t>(std::max<int64_t>(c.offset, 0), len);
+  p.e = std::min<int64_t>(std::max<int64_t>((int64_t)c.offset + c.bytes, p.s), len);
+  p.bin = std::min<uint32_t>(c.lang1, CLD_NUM_LANGUAGES);
+  return p;
+}
+int64_t host_doc_len(const uint64_t* offsets, size_t i) {
+  return offsets[i + 1] > offsets[i] ? (int64_t)(offsets[i + 1] - offsets[i]) : 0;
+}
+bool chunk_args_bad(const uint64_t* offsets, size_t n, const cld_chunk* chunks, uint64_t chunk_cap,
+                    const uint64_t* chunk_offsets) {
+  return n > 0x7FFFFFFFu || chunk_cap > 0xFFFFFFFFull || !chunk_offsets ||
+         (n > 0 && (!offsets || (chunk_cap > 0 && !chunks)));
+}
+}  // namespace
+
+int cld_chunk_totals(const uint64_t* offsets, size_t n, const cld_chunk* chunks, uint64_t chunk_cap,
+                     const uint64_t* chunk_offsets, uint64_t* chunk_counts, uint64_t* chunk_bytes) {
+  if (chunk_args_bad(offsets, n, chunks, chunk_cap, chunk_offsets)) return CLD_EINVAL;
+  if (chunk_counts) std::fill(chunk_counts, chunk_counts + CLD_GROUP_BINS, 0);
+  if (chunk_bytes) std::fill(chunk_bytes, chunk_bytes + CLD_GROUP_BINS, 0);
+  for (size_t i = 0; i < n; ++i) {
+    const int64_t len = host_doc_len(offsets, i);
+    const uint64_t end = std::min(chunk_offsets[i + 1], chunk_cap);
+    for (uint64_t c = chunk_offsets[i]; c < end; ++c) {
+      const HostPiece p = host_piece(chunks[c], len);
+      if (chunk_counts) ++chunk_counts[p.bin];
+      if (chunk_bytes) chunk_bytes[p.bin] += (uint64_t)(p.e - p.s);
+    }
+  }
+  return CLD_OK;
+}
+
+int cld_gather_chunks(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_chunk* chunks,
+                      uint64_t chunk_cap, const uint64_t* chunk_offsets, const uint8_t* select, uint32_t flags,
+                      uint8_t* out_buf, uint64_t out_cap, uint64_t* out_offsets) {
+  if (chunk_args_bad(offsets, n, chunks, chunk_cap, chunk_offsets) || (flags & ~CLD_CHUNKS_SPACE) != 0 || !select ||
+      (out_cap > 0 && !out_buf) || (n > 0 && (!out_offsets || (out_cap > 0 && !buf))))
+    return CLD_EINVAL;
+  uint64_t at = 0;
+  auto put = [&](uint8_t b) {
+    if (at < out_cap) out_buf[at] = b;
+    ++at;
+  };
+  if (out_offsets) out_offsets[0] = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const int64_t len = host_doc_len(offsets, i);
+    const uint8_t* doc = buf ? buf + offsets[i] : nullptr;   // (only read with out_cap > 0)
+    const uint64_t first = chunk_offsets[i], end = std::min(chunk_offsets[i + 1], chunk_cap);
+    bool prev_kept = false;
+    int64_t prev_e = 0;
+    for (uint64_t c = first; c < end; ++c) {
+      const HostPiece p = host_piece(chunks[c], len);
+      const bool kept = select[p.bin] != 0 && p.e > p.s;
+      if (kept) {
+        if ((flags & CLD_CHUNKS_SPACE) && c != first && !(prev_kept && prev_e == p.s)) put(0x20);
+        if (out_cap == 0) at += (uint64_t)(p.e - p.s);
+        else for (int64_t k = p.s; k < p.e; ++k) put(doc[k]);
+      }
+      prev_kept = kept;
+      prev_e = p.e;
+    }
+    out_offsets[i + 1] = at;
+  }
+  return CLD_OK;
+}
+
+int cld_chunk_totals_device(int device, const uint64_t* d_offsets, size_t n, const cld_chunk* d_chunks,
+                            uint64_t chunk_cap, const uint64_t* d_chunk_offsets, uint64_t* d_chunk_counts,
+                            uint64_t* d_chunk_bytes, void* d_work, size_t work_bytes, void* stream) {
+  if (chunk_args_bad(d_offsets, n, d_chunks, chunk_cap, d_chunk_offsets) ||
+      (n > 0 && (!d_work || ((uintptr_t)d_work & 7))))
+    return CLD_EINVAL;
+  if (n > 0 && work_bytes < cld_chunk_work_bytes(n, chunk_cap)) return CLD_ENOSPC;
+  int rc = cld_init(nullptr, 0);
+  if (rc) return rc;
+  if (device < 0 || device >= (int)g_devs.size()) return CLD_EINVAL;
+  Device* d = g_devs[device];
+  HIP_OK(hipSetDevice(d->id));
+  hipStream_t s = stream ? (hipStream_t)stream : d->stream;
+  if (n == 0) {
+    if (d_chunk_counts) HIP_OK(hipMemsetAsync(d_chunk_counts, 0, CLD_GROUP_BINS * sizeof(uint64_t), s));
+    if (d_chunk_bytes) HIP_OK(hipMemsetAsync(d_chunk_bytes, 0, CLD_GROUP_BINS * sizeof(uint64_t), s));
+    return CLD_OK;
+  }
+  // (no scratch of the context is used: nothing to serialise with other batches)
+  HIP_OK(cld_launch_chunk_totals(d_offsets, (uint32_t)n, d_chunks, d_chunk_offsets, chunk_cap, d_chunk_counts,
+                                 d_chunk_bytes, d_work, s));
+  return CLD_OK;
+}
+
+int cld_gather_chunks_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n,
+                             const cld_chunk* d_chunks, uint64_t chunk_cap, const uint64_t* d_chunk_offsets,
+                             const uint8_t* d_select, uint32_t flags, uint8_t* d_out_buf, uint64_t out_cap,
+                             uint64_t* d_out_offsets, void* d_work, size_t work_bytes, void* stream) {
+  if (chunk_args_bad(d_offsets, n, d_chunks, chunk_cap, d_chunk_offsets) || (flags & ~CLD_CHUNKS_SPACE) != 0 ||
+      !d_select || (out_cap > 0 && !d_out_buf) ||
+      (n > 0 && (!d_out_offsets || ((uintptr_t)d_out_offsets & 7) || !d_work || ((uintptr_t)d_work & 7) ||
+                 (out_cap > 0 && !d_buf))))
+    return CLD_EINVAL;
+  if (n > 0 && work_bytes < cld_chunk_work_bytes(n, chunk_cap)) return CLD_ENOSPC;
+  int rc = cld_init(nullptr, 0);
+  if (rc) return rc;
+  if (device < 0 || device >= (int)g_devs.size()) return CLD_EINVAL;
+  Device* d = g_devs[device];
+  HIP_OK(hipSetDevice(d->id));
+  hipStream_t s = stream ? (hipStream_t)stream : d->stream;
+  if (n == 0) {
+    if (d_out_offsets) HIP_OK(hipMemsetAsync(d_out_offsets, 0, sizeof(uint64_t), s));
+    return CLD_OK;
+  }
+  HIP_OK(cld_launch_chunk_gather(d_buf, d_offsets, (uint32_t)n, d_chunks, d_chunk_offsets, chunk_cap, d_select, flags,
+                                 d_out_buf, out_cap, d_out_offsets, d_work, s));
+  return CLD_OK;
+}
+
 int cld_detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
                          uint32_t flags, cld_result* out, cld_chunk* chunks, size_t chunk_cap,
                          uint64_t* chunk_offsets) {
