@@ -686,6 +686,98 @@ int cld_gather_chunks_device(int device, const uint8_t* d_buf, const uint64_t* d
                              const uint8_t* d_select, uint32_t flags, uint8_t* d_out_buf, uint64_t out_cap,
                              uint64_t* d_out_offsets, void* d_work, size_t work_bytes, void* stream);
 
+/* A batch split into lines, for line-level detection without leaving the GPU:
+ * each line of a page is one independent document for the detect entries (a
+ * crawl pipeline's usual question is the language of each line or paragraph).
+ * The split is zero-copy: a line keeps its terminating LF, so the lines tile
+ * the text exactly and the line batch is the same buf with a new offsets array.
+ *
+ * The batch is buf, offsets[0..n], non-decreasing as for every entry; its text
+ * is T = [offsets[0], offsets[n]).
+ *   boundaries   B is the set of distinct values of offsets[0..n], plus p + 1
+ *                for every p in T with buf[p] == 0x0A.  No other byte is
+ *                special: CR stays in its line, NUL is an ordinary byte.
+ *   lines        are the consecutive pairs of sorted B, m = |B| - 1 of them.  A
+ *                line includes its LF; a document's last line may lack one; an
+ *                empty document has no line; no line crosses a document.
+ *   CLD_LINES_JOIN_BLANK  an LF boundary p + 1 that is not a value of offsets is
+ *                dropped when the raw line it ends is blank: the raw line runs
+ *                from the largest element of the unflagged B that is <= p
+ *                through p, and is blank when it has no byte above 0x20.  Blank
+ *                lines therefore join the line after them, blank lines at a
+ *                document's end form one line, and every line of a document
+ *                except its last holds a byte above 0x20.  Any other flag bit:
+ *                CLD_EINVAL.
+ *   line_offsets[0..m]  sorted B: line_offsets[0] == offsets[0], line_offsets[m]
+ *                == offsets[n].  (buf, line_offsets, m) is a batch for every
+ *                cld_detect_batch_device*, group and gather entry.
+ *   doc_lines[0..n]  the number of elements of B below offsets[i]: document i's
+ *                lines are [doc_lines[i], doc_lines[i + 1]),
+ *                line_offsets[doc_lines[i]] == offsets[i], doc_lines[n] == m.
+ *   line_doc[0..m)  (NULL: not wanted) the document of each line.
+ *   status       (NULL: not wanted) total_lines = m and max_line_bytes, the
+ *                longest line.
+ * Capacity, as for the chunk vectors: line_offsets holds line_cap + 1 words and
+ * line_doc line_cap; doc_lines and status always receive the true values;
+ * line_offsets[j] is written for j <= min(m, line_cap), line_doc[j] for j <
+ * min(m, line_cap), and nothing past those extents.  line_cap == 0 with
+ * line_offsets NULL is the sizing pass: read total_lines, allocate, call again.
+ * line_cap > INT32_MAX is CLD_EINVAL: the line batch must be a legal n for the
+ * detect entries.
+ * cld_split_lines is the host reference, no GPU.  cld_split_lines_device:
+ * every pointer in device memory of GPU `device` (8-byte aligned where it holds
+ * 64-bit words), enqueued on `stream` (NULL: the runtime's); asynchronous, the
+ * host waits for nothing and reads no device word; none of the context's
+ * scratch is used, so it may run from several threads, each with a workspace of
+ * its own.  buf_bytes bounds d_offsets[n]: every offset is clamped to it, so no
+ * offsets word makes a kernel read outside d_buf[0, buf_bytes) or write outside
+ * the extents above; where the offsets go down the values are unspecified and
+ * the bounds still hold.  The output is the same from run to run: no atomic
+ * decides a position (the longest line is an integer maximum).  d_work holds
+ * work_bytes >= cld_lines_work_bytes(n, buf_bytes) bytes (a smaller one:
+ * CLD_ENOSPC, nothing enqueued) and is free again when the call's work on the
+ * stream is done: cld_lines_work_bytes is 8 * (buf_bytes / 1024 + 3) + 73728 --
+ * one word per 1 KB tile of the text, the per-range sums and a word per wave --
+ * whatever n and line_cap are.
+ * CLD_EINVAL: n > INT32_MAX, line_cap > INT32_MAX, unknown flag bits, line_cap
+ * > 0 with NULL line_offsets; with n > 0 a NULL or not 8-byte aligned offsets,
+ * doc_lines or workspace (the host entry has no workspace); with n > 0 and
+ * buf_bytes > 0 a NULL buf (the host entry: with offsets[n] > offsets[0]).
+ * n == 0: CLD_OK, with doc_lines[0] = 0 and a zero status; line_offsets[0] is
+ * left alone, there is no offsets[0] to copy.
+ *
+ * cld_lines_to_chunks (host) / cld_lines_to_chunks_device turn the results of
+ * the line batch into one cld_chunk vector per document of the original batch,
+ * so cld_chunk_totals* and cld_gather_chunks* work at line granularity and keep
+ * document identity.  chunks[j] is written for j < min(doc_lines[n], line_cap);
+ * with i = line_doc[j]: offset = line_offsets[j] - offsets[i] saturated to
+ * [0, INT32_MAX], bytes = the line's length saturated to INT32_MAX, lang1 = the
+ * key of line_results[j] exactly as cld_group_by_language defines it
+ * (group_flags: CLD_GROUP_TOP1, CLD_GROUP_RELIABLE_ONLY; other bits:
+ * CLD_EINVAL), pad = 0; i >= n gives {0, 0, key, 0}.  The chunk offsets of
+ * these vectors are doc_lines itself and chunk_cap is line_cap: nothing is
+ * copied.  One lane per line, no workspace; stream and device as above.
+ * CLD_EINVAL: n or line_cap > INT32_MAX, NULL doc_lines; with n > 0 and
+ * line_cap > 0 a NULL line_results, line_offsets, line_doc, offsets or chunks. */
+#define CLD_LINES_JOIN_BLANK 1u         /* blank lines join the line after them */
+typedef struct cld_lines_status {
+  uint64_t total_lines;                 /* m = doc_lines[n]; > line_cap: call again with more room */
+  uint64_t max_line_bytes;              /* the longest line */
+} cld_lines_status;
+size_t cld_lines_work_bytes(size_t n, uint64_t buf_bytes);
+int cld_split_lines(const uint8_t* buf, const uint64_t* offsets, size_t n, uint32_t flags, uint64_t* line_offsets,
+                    uint32_t* line_doc, uint64_t line_cap, uint64_t* doc_lines, cld_lines_status* status);
+int cld_split_lines_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n, uint64_t buf_bytes,
+                           uint32_t flags, uint64_t* d_line_offsets, uint32_t* d_line_doc, uint64_t line_cap,
+                           uint64_t* d_doc_lines, cld_lines_status* d_status, void* d_work, size_t work_bytes,
+                           void* stream);
+int cld_lines_to_chunks(const cld_result* line_results, const uint64_t* line_offsets, const uint32_t* line_doc,
+                        uint64_t line_cap, const uint64_t* offsets, size_t n, const uint64_t* doc_lines,
+                        uint32_t group_flags, cld_chunk* chunks);
+int cld_lines_to_chunks_device(int device, const cld_result* d_line_results, const uint64_t* d_line_offsets,
+                               const uint32_t* d_line_doc, uint64_t line_cap, const uint64_t* d_offsets, size_t n,
+                               const uint64_t* d_doc_lines, uint32_t group_flags, cld_chunk* d_chunks, void* stream);
+
 /* The preparation step alone, on GPU 0 (host buffers): out_buf receives the
  * prepared documents back to back (capacity >= offsets[n]-offsets[0] + n
  * bytes), out_offsets[0..n] their offsets.  flags: CLD_FLAG_STRIP_EXTRAS and/or

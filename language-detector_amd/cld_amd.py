@@ -19,6 +19,9 @@ Mirrors the reference's caller-facing interface for this path:
   chunk_totals / gather_chunks            per-language totals over chunk vectors, and the pieces in chosen
                                           languages packed into a new batch (host references)
   chunk_totals_device / gather_chunks_device      the same over a batch and its vectors in HBM
+  split_lines / lines_to_chunks           a batch's lines as a new offsets array over the same text, and
+                                          per-line results as one chunk vector per document (host references)
+  split_lines_device / lines_to_chunks_device     the same over a batch in HBM: line-level detection
   detect_language_scrubbed(text)          the repair on the host, then detect_language
 There is no CPU fallback: if the HIP library or a GPU is missing, calls raise.
 """
@@ -74,8 +77,14 @@ EXPORTS = ("detect_language", "cld_init", "cld_init_device", "cld_shutdown", "cl
            "cld_detect_batch_device_vec_docflags", "cld_scrub_utf8_host", "cld_scrub_utf8_batch",
            "cld_scrub_utf8_device", "detect_language_scrubbed", "cld_group_work_bytes", "cld_group_by_language",
            "cld_group_by_language_device", "cld_gather_docs_device", "cld_last_route_stats", "cld_chunk_work_bytes",
-           "cld_chunk_totals", "cld_chunk_totals_device", "cld_gather_chunks", "cld_gather_chunks_device")
+           "cld_chunk_totals", "cld_chunk_totals_device", "cld_gather_chunks", "cld_gather_chunks_device",
+           "cld_lines_work_bytes", "cld_split_lines", "cld_split_lines_device", "cld_lines_to_chunks",
+           "cld_lines_to_chunks_device")
 CHUNK_DTYPE = np.dtype([("offset", "<i4"), ("bytes", "<i4"), ("lang1", "<u2"), ("pad", "<u2")])   # cld_chunk
+LINES_JOIN_BLANK = 1       # include/cld_mi355x.h CLD_LINES_JOIN_BLANK: blank lines join the line after them
+LINES_TILE = 1024          # csrc/cld_kernels.h kLinesTile: the text bytes one wave of the split reads
+LINES_WGS = 256            # csrc/cld_kernels.h kLinesWgs: the split scans its tiles in at most this many ranges
+LINES_STATUS_DTYPE = np.dtype([("total_lines", "<u8"), ("max_line_bytes", "<u8")])   # cld_lines_status
 
 
 class Hints(ctypes.Structure):
@@ -248,6 +257,12 @@ def lib():
         L.cld_chunk_totals_device.argtypes = [ctypes.c_int, vp, sz, vp, u64, vp, vp, vp, vp, sz, vp]
         L.cld_gather_chunks.argtypes = [vp, vp, sz, vp, u64, vp, vp, u32, vp, u64, vp]
         L.cld_gather_chunks_device.argtypes = [ctypes.c_int, vp, vp, sz, vp, u64, vp, vp, u32, vp, u64, vp, vp, sz, vp]
+        L.cld_lines_work_bytes.argtypes = [sz, u64]
+        L.cld_lines_work_bytes.restype = sz
+        L.cld_split_lines.argtypes = [vp, vp, sz, u32, vp, vp, u64, vp, vp]
+        L.cld_split_lines_device.argtypes = [ctypes.c_int, vp, vp, sz, u64, u32, vp, vp, u64, vp, vp, vp, sz, vp]
+        L.cld_lines_to_chunks.argtypes = [vp, vp, vp, u64, vp, sz, vp, u32, vp]
+        L.cld_lines_to_chunks_device.argtypes = [ctypes.c_int, vp, vp, vp, u64, vp, sz, vp, u32, vp, vp]
         _lib = L
     return _lib
 
@@ -825,6 +840,91 @@ def gather_chunks_device(device, d_buf_ptr, d_offsets_ptr, n, d_chunks_ptr, chun
                                         d_out_offsets_ptr, d_work_ptr, work_bytes, stream_ptr)
     if rc != 0:
         raise CldError("cld_gather_chunks_device failed: %d" % rc)
+
+
+def lines_work_bytes(n, buf_bytes):
+    """cld_lines_work_bytes: the workspace cld_split_lines_device needs: one word per LINES_TILE bytes and a fixed part."""
+    return int(lib().cld_lines_work_bytes(n, buf_bytes))
+
+
+def split_lines(buf, offsets, flags=0, line_cap=None):
+    """cld_split_lines (the host reference, no GPU): the batch's lines, each with its LF, as a new offsets
+    array over the same buffer -> dict of line_offsets uint64[min(m, line_cap) + 1], line_doc
+    uint32[min(m, line_cap)], doc_lines uint64[n + 1] and status (a LINES_STATUS_DTYPE record).
+    flags: LINES_JOIN_BLANK.  line_cap: the room for lines (default: the sizing pass first, then all of
+    them); doc_lines and status are the true values either way."""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if len(offsets) < 1:
+        raise ValueError("need n + 1 offsets")
+    n = len(offsets) - 1
+    doc_lines = np.zeros(n + 1, np.uint64)
+    status = np.zeros(1, LINES_STATUS_DTYPE)
+
+    def call(lo, ld, cap):
+        rc = lib().cld_split_lines(buf.ctypes.data, offsets.ctypes.data, n, flags, lo.ctypes.data if lo is not None else None,
+                                   ld.ctypes.data if ld is not None else None, cap, doc_lines.ctypes.data,
+                                   status.ctypes.data)
+        if rc != 0:
+            raise CldError("cld_split_lines failed: %d" % rc)
+
+    if line_cap is None:
+        call(None, None, 0)
+        line_cap = int(status[0]["total_lines"])
+    line_offsets = np.zeros(line_cap + 1, np.uint64)
+    line_doc = np.zeros(max(line_cap, 1), np.uint32)
+    call(line_offsets, line_doc, line_cap)
+    m = min(int(status[0]["total_lines"]), line_cap)
+    return {"line_offsets": line_offsets[:m + 1], "line_doc": line_doc[:m], "doc_lines": doc_lines, "status": status[0]}
+
+
+def split_lines_device(device, d_buf_ptr, d_offsets_ptr, n, buf_bytes, d_line_offsets_ptr, d_line_doc_ptr, line_cap,
+                       d_doc_lines_ptr, d_work_ptr, work_bytes, flags=0, d_status_ptr=None, stream_ptr=None):
+    """cld_split_lines_device: every pointer in device memory (line_offsets uint64[line_cap + 1], line_doc
+    uint32[line_cap] or None, doc_lines uint64[n + 1], status a LINES_STATUS_DTYPE record or None, a
+    workspace of lines_work_bytes(n, buf_bytes)); line_cap 0 with no line_offsets sizes the output.
+    flags: LINES_JOIN_BLANK.  Asynchronous on the stream."""
+    rc = lib().cld_split_lines_device(device, d_buf_ptr, d_offsets_ptr, n, buf_bytes, flags, d_line_offsets_ptr,
+                                      d_line_doc_ptr, line_cap, d_doc_lines_ptr, d_status_ptr, d_work_ptr, work_bytes,
+                                      stream_ptr)
+    if rc != 0:
+        raise CldError("cld_split_lines_device failed: %d" % rc)
+
+
+def lines_to_chunks(line_results, line_offsets, line_doc, offsets, doc_lines, flags=0, line_cap=None):
+    """cld_lines_to_chunks (the host reference, no GPU): the results of a line batch (RESULT_DTYPE, one per
+    line) as one CHUNK_DTYPE vector per document of the original batch; the vectors' chunk offsets are
+    doc_lines itself.  flags: GROUP_TOP1 | GROUP_RELIABLE_ONLY.  line_cap: the lines that exist (default:
+    all of line_doc) -> CHUNK_DTYPE[min(doc_lines[n], line_cap)]."""
+    line_results = np.ascontiguousarray(line_results, dtype=RESULT_DTYPE)
+    line_offsets = np.ascontiguousarray(line_offsets, dtype=np.uint64)
+    line_doc = np.ascontiguousarray(line_doc, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    doc_lines = np.ascontiguousarray(doc_lines, dtype=np.uint64)
+    if len(offsets) < 1 or len(doc_lines) != len(offsets):
+        raise ValueError("need n + 1 offsets and n + 1 doc_lines")
+    cap = len(line_doc) if line_cap is None else int(line_cap)
+    if cap > len(line_doc) or cap > len(line_results) or cap + 1 > len(line_offsets) + (cap == 0):
+        raise ValueError("line_cap is more than the lines given")
+    n = len(offsets) - 1
+    m = min(int(doc_lines[n]), cap)
+    chunks = np.zeros(max(m, 1), CHUNK_DTYPE)
+    rc = lib().cld_lines_to_chunks(line_results.ctypes.data, line_offsets.ctypes.data, line_doc.ctypes.data, cap,
+                                   offsets.ctypes.data, n, doc_lines.ctypes.data, flags, chunks.ctypes.data)
+    if rc != 0:
+        raise CldError("cld_lines_to_chunks failed: %d" % rc)
+    return chunks[:m]
+
+
+def lines_to_chunks_device(device, d_line_results_ptr, d_line_offsets_ptr, d_line_doc_ptr, line_cap, d_offsets_ptr, n,
+                           d_doc_lines_ptr, d_chunks_ptr, flags=0, stream_ptr=None):
+    """cld_lines_to_chunks_device: every pointer in device memory (results cld_result[line_cap], line_offsets
+    uint64[line_cap + 1], line_doc uint32[line_cap], the original batch's offsets and doc_lines uint64[n + 1],
+    chunks cld_chunk[line_cap]); asynchronous on the stream."""
+    rc = lib().cld_lines_to_chunks_device(device, d_line_results_ptr, d_line_offsets_ptr, d_line_doc_ptr, line_cap,
+                                          d_offsets_ptr, n, d_doc_lines_ptr, flags, d_chunks_ptr, stream_ptr)
+    if rc != 0:
+        raise CldError("cld_lines_to_chunks_device failed: %d" % rc)
 
 
 def valid_prefix_host(doc):

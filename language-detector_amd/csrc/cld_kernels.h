@@ -248,6 +248,31 @@ hipError_t cld_launch_chunk_totals(const uint64_t* offs, uint32_t n, const cld_c
 hipError_t cld_launch_chunk_gather(const uint8_t* buf, const uint64_t* offs, uint32_t n, const cld_chunk* chunks,
                                    const uint64_t* chunk_offs, uint64_t chunk_cap, const uint8_t* select, uint32_t flags,
                                    uint8_t* out, uint64_t out_cap, uint64_t* out_offs, void* work, hipStream_t s);
+// cld_split_lines_device / cld_lines_to_chunks_device (cld_lines.hip).  The
+// text is read in tiles of kLinesTile bytes, one wave each; the tile words are
+// scanned over at most kLinesWgs ranges of tiles.  `work` (cld_lines_work(buf_bytes)
+// bytes, 8-byte aligned, not zeroed): a fixed part -- the per-range maxima and
+// sums, the longest line of each of at most kLinesWaves waves -- then one u64
+// per tile and one more.  buf_bytes
+// bounds offs[n]; the text has at most buf_bytes / kLinesTile + 2 tiles (a
+// 16-byte skew and a ragged end).  n, line_cap <= INT32_MAX.
+// cld_launch_split_lines: line_offsets, line_doc, status each nullable;
+// max_wgs (0: as many as stay resident): a cap on the workgroups of the two
+// text kernels, so that a test gives every wave a run of many tiles at a
+// small size.
+constexpr int kLinesTile = 1024;
+constexpr int kLinesWgs = kGroupWgs;
+constexpr int kLinesWaves = 8192;
+constexpr size_t kLinesWorkFixed = 8192 + kLinesWaves * sizeof(uint64_t);
+inline size_t cld_lines_work(uint64_t buf_bytes) {
+  return kLinesWorkFixed + (size_t)(buf_bytes / kLinesTile + 3) * sizeof(uint64_t);
+}
+hipError_t cld_launch_split_lines(const uint8_t* buf, const uint64_t* offs, uint32_t n, uint64_t buf_bytes, uint32_t flags,
+                                  uint64_t* line_offsets, uint32_t* line_doc, uint64_t line_cap, uint64_t* doc_lines,
+                                  cld_lines_status* status, void* work, uint32_t max_wgs, hipStream_t s);
+hipError_t cld_launch_lines_to_chunks(const cld_result* res, const uint64_t* line_offsets, const uint32_t* line_doc,
+                                      uint64_t line_cap, const uint64_t* offs, uint32_t n, const uint64_t* doc_lines,
+                                      uint32_t group_flags, cld_chunk* chunks, hipStream_t s);
 // ApplyHints (cld_hints.hip; compact_lang_det_impl.cc:1587-1684), one wave
 // per document: priors14 (14 per document, trimmed to 4, zero-padded),
 // boosts16 (the 16 langprobs enqueue() takes as `priors`) and special (the

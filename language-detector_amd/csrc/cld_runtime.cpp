@@ -2838,6 +2838,140 @@ int cld_gather_chunks_device(int device, const uint8_t* d_buf, const uint64_t* d
   return CLD_OK;
 }
 
+size_t cld_lines_work_bytes(size_t n, uint64_t buf_bytes) {
+  (void)n;   // one word per tile of the text and a fixed number of ranges whatever n is (cld_kernels.h)
+  return cld_lines_work(buf_bytes);
+}
+
+namespace {
+// Test hook of cld_split_lines_device, read once per process: CLD_LINES_WGS=k caps
+// the workgroups of its two text kernels at k, so that each wave takes a run of
+// many consecutive tiles at a small size (tests/test_gpu_lines.py); 0: no cap.
+uint32_t lines_max_wgs() {
+  static const uint32_t v = (uint32_t)std::max<long>(env_long("CLD_LINES_WGS", 0), 0);
+  return v;
+}
+bool lines_args_bad(const uint64_t* offsets, size_t n, uint32_t flags, const uint64_t* line_offsets, uint64_t line_cap,
+                    const uint64_t* doc_lines) {
+  return n > 0x7FFFFFFFu || line_cap > 0x7FFFFFFFull || (flags & ~CLD_LINES_JOIN_BLANK) != 0 ||
+         (line_cap > 0 && !line_offsets) ||
+         (n > 0 && (!offsets || ((uintptr_t)offsets & 7) || !doc_lines || ((uintptr_t)doc_lines & 7)));
+}
+bool lines_chunks_args_bad(const cld_result* res, const uint64_t* line_offsets, const uint32_t* line_doc,
+                           uint64_t line_cap, const uint64_t* offsets, size_t n, const uint64_t* doc_lines,
+                           uint32_t group_flags, const cld_chunk* chunks) {
+  return n > 0x7FFFFFFFu || line_cap > 0x7FFFFFFFull ||
+         (group_flags & ~(CLD_GROUP_TOP1 | CLD_GROUP_RELIABLE_ONLY)) != 0 || !doc_lines ||
+         (n > 0 && line_cap > 0 && (!res || !line_offsets || !line_doc || !offsets || !chunks));
+}
+}  // namespace
+
+// The host reference of the split, written from the definitions in cld_mi355x.h: one pass over the text.
+int cld_split_lines(const uint8_t* buf, const uint64_t* offsets, size_t n, uint32_t flags, uint64_t* line_offsets,
+                    uint32_t* line_doc, uint64_t line_cap, uint64_t* doc_lines, cld_lines_status* status) {
+  if (lines_args_bad(offsets, n, flags, line_offsets, line_cap, doc_lines) ||
+      (n > 0 && offsets[n] > offsets[0] && !buf))
+    return CLD_EINVAL;
+  if (n == 0) {
+    if (doc_lines) doc_lines[0] = 0;
+    if (status) status->total_lines = status->max_line_bytes = 0;
+    return CLD_OK;
+  }
+  uint64_t m = 0, longest = 0, start = offsets[0];
+  auto boundary = [&](uint64_t b, size_t doc) {          // b begins line m, in document doc
+    if (m > 0) longest = std::max(longest, b - start);
+    start = b;
+    if (line_offsets && m <= line_cap) line_offsets[m] = b;
+    if (line_doc && m < line_cap) line_doc[m] = (uint32_t)doc;
+    ++m;
+  };
+  for (size_t i = 0; i < n; ++i) {
+    doc_lines[i] = m;
+    const uint64_t a = offsets[i], e = offsets[i + 1];
+    if (e <= a) continue;
+    boundary(a, i);
+    bool nonblank = false;                               // of the raw line so far
+    for (uint64_t p = a; p < e; ++p) {
+      if (buf[p] > 0x20) nonblank = true;
+      if (buf[p] != 0x0A) continue;
+      if (p + 1 < e && (nonblank || !(flags & CLD_LINES_JOIN_BLANK))) boundary(p + 1, i);
+      nonblank = false;
+    }
+  }
+  doc_lines[n] = m;
+  if (m > 0) longest = std::max(longest, offsets[n] - start);
+  if (line_offsets && m <= line_cap) line_offsets[m] = offsets[n];
+  if (status) {
+    status->total_lines = m;
+    status->max_line_bytes = longest;
+  }
+  return CLD_OK;
+}
+
+int cld_split_lines_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n, uint64_t buf_bytes,
+                           uint32_t flags, uint64_t* d_line_offsets, uint32_t* d_line_doc, uint64_t line_cap,
+                           uint64_t* d_doc_lines, cld_lines_status* d_status, void* d_work, size_t work_bytes,
+                           void* stream) {
+  if (lines_args_bad(d_offsets, n, flags, d_line_offsets, line_cap, d_doc_lines) ||
+      (n > 0 && (!d_work || ((uintptr_t)d_work & 7) || (buf_bytes > 0 && !d_buf))))
+    return CLD_EINVAL;
+  if (n > 0 && work_bytes < cld_lines_work_bytes(n, buf_bytes)) return CLD_ENOSPC;
+  int rc = cld_init(nullptr, 0);
+  if (rc) return rc;
+  if (device < 0 || device >= (int)g_devs.size()) return CLD_EINVAL;
+  Device* d = g_devs[device];
+  HIP_OK(hipSetDevice(d->id));
+  hipStream_t s = stream ? (hipStream_t)stream : d->stream;
+  if (n == 0) {
+    if (d_doc_lines) HIP_OK(hipMemsetAsync(d_doc_lines, 0, sizeof(uint64_t), s));
+    if (d_status) HIP_OK(hipMemsetAsync(d_status, 0, sizeof(cld_lines_status), s));
+    return CLD_OK;
+  }
+  // (no scratch of the context is used: nothing to serialise with other batches)
+  HIP_OK(cld_launch_split_lines(d_buf, d_offsets, (uint32_t)n, buf_bytes, flags, d_line_offsets, d_line_doc, line_cap,
+                                d_doc_lines, d_status, d_work, lines_max_wgs(), s));
+  return CLD_OK;
+}
+
+int cld_lines_to_chunks(const cld_result* line_results, const uint64_t* line_offsets, const uint32_t* line_doc,
+                        uint64_t line_cap, const uint64_t* offsets, size_t n, const uint64_t* doc_lines,
+                        uint32_t group_flags, cld_chunk* chunks) {
+  if (lines_chunks_args_bad(line_results, line_offsets, line_doc, line_cap, offsets, n, doc_lines, group_flags, chunks))
+    return CLD_EINVAL;
+  if (n == 0 || line_cap == 0) return CLD_OK;
+  const uint64_t m = std::min(doc_lines[n], line_cap);
+  for (uint64_t j = 0; j < m; ++j) {
+    uint32_t key = (group_flags & CLD_GROUP_TOP1) ? line_results[j].lang3[0] : line_results[j].summary_lang;
+    if ((group_flags & CLD_GROUP_RELIABLE_ONLY) && line_results[j].is_reliable == 0) key = 26;   // UNKNOWN_LANGUAGE
+    const uint32_t i = line_doc[j];
+    cld_chunk c = {0, 0, (uint16_t)key, 0};
+    if (i < n) {
+      const uint64_t a = line_offsets[j], b = line_offsets[j + 1], o = offsets[i];
+      c.offset = (int32_t)std::min<uint64_t>(a > o ? a - o : 0, 0x7FFFFFFF);
+      c.bytes = (int32_t)std::min<uint64_t>(b > a ? b - a : 0, 0x7FFFFFFF);
+    }
+    chunks[j] = c;
+  }
+  return CLD_OK;
+}
+
+int cld_lines_to_chunks_device(int device, const cld_result* d_line_results, const uint64_t* d_line_offsets,
+                               const uint32_t* d_line_doc, uint64_t line_cap, const uint64_t* d_offsets, size_t n,
+                               const uint64_t* d_doc_lines, uint32_t group_flags, cld_chunk* d_chunks, void* stream) {
+  if (lines_chunks_args_bad(d_line_results, d_line_offsets, d_line_doc, line_cap, d_offsets, n, d_doc_lines, group_flags,
+                            d_chunks))
+    return CLD_EINVAL;
+  int rc = cld_init(nullptr, 0);
+  if (rc) return rc;
+  if (device < 0 || device >= (int)g_devs.size()) return CLD_EINVAL;
+  if (n == 0 || line_cap == 0) return CLD_OK;
+  Device* d = g_devs[device];
+  HIP_OK(hipSetDevice(d->id));
+  HIP_OK(cld_launch_lines_to_chunks(d_line_results, d_line_offsets, d_line_doc, line_cap, d_offsets, (uint32_t)n,
+                                    d_doc_lines, group_flags, d_chunks, stream ? (hipStream_t)stream : d->stream));
+  return CLD_OK;
+}
+
 int cld_detect_batch_vec(const uint8_t* buf, const uint64_t* offsets, size_t n, const cld_hints* hints,
                          uint32_t flags, cld_result* out, cld_chunk* chunks, size_t chunk_cap,
                          uint64_t* chunk_offsets) {
