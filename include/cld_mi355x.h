@@ -778,6 +778,110 @@ int cld_lines_to_chunks_device(int device, const cld_result* d_line_results, con
                                const uint32_t* d_line_doc, uint64_t line_cap, const uint64_t* d_offsets, size_t n,
                                const uint64_t* d_doc_lines, uint32_t group_flags, cld_chunk* d_chunks, void* stream);
 
+/* The text of HTML pages, with a map back to the page: what the group, chunk
+ * and line entries above need in front of them when the batch is HTML (they
+ * take their batch as plain text), without leaving the GPU.
+ *
+ * text(page) is what the reference's span scanner reads of a page in HTML mode
+ * (is_plain_text = false) before it looks at letters or scripts: one
+ * left-to-right walk (getonescriptspan.cc:150-203, 393-468, 503-541) over the
+ * page bytes [0, L), from p = 0:
+ *   '<'          a '<' the walk reaches starts a tag of t =
+ *                ScanToPossibleLetter(page + p, L - p) bytes, t >= 1: comments,
+ *                <script>...</script> and <style>...</style> bodies and quoted
+ *                attributes exactly as the reference's tag parser consumes
+ *                them.  It emits one separator byte, 0x20 -- or 0x0A under
+ *                CLD_HTMLTEXT_BLOCK_LF when the tag is a block tag -- with
+ *                source position p; the walk continues at p + t.
+ *   '&'          a '&' the walk reaches is read by EntityToBuffer.  A decodable
+ *                entity consumes tlen bytes and emits its plen decoded UTF-8
+ *                bytes, byte k with source position p + k.  An undecodable '&'
+ *                consumes one byte and emits nothing: the scanner drops it and
+ *                the run of letters goes on ("AT&T" reads "ATT"), so that the
+ *                text scores as the page scores.
+ *   other bytes  emit themselves, with source position p.
+ * Nothing is read outside the page: a tag left open at the page's end consumes
+ * to L and no further, an entity is cut at L.
+ * No growth: a decoded entity never holds more bytes than it consumed (the
+ * shortest forms are "&#9" 3 -> 1, "&lt" 4 -> 2, "&ni;" 4 -> 3, "&#65536"
+ * 7 -> 4), so text_len <= L and the source positions are strictly increasing.
+ * Block tags: the bytes after '<' or '</' spell one of CLD_HTMLTEXT_BLOCK_TAGS,
+ * ASCII case-insensitive, followed by a byte that is not an ASCII letter or
+ * digit, or by the page end.  Comments and every other tag give a space.  Space
+ * and LF are both non-letters to the detector: the flag changes no detection
+ * result, it gives cld_split_lines* the lines of the text.
+ * Every page is extracted whatever its bytes are (tags and entities are a
+ * matter of bytes; the well-formedness of the UTF-8 around them plays no part).
+ *
+ * The output is page-aligned -- no sizing pass, no workspace:
+ *   out          page i's text is out[offsets[i] .. offsets[i] + text_len[i]);
+ *                the rest of the page's range is filled with 0x20.  (out,
+ *                offsets, n) is at once a batch for every
+ *                cld_detect_batch_device*, group, gather and line entry:
+ *                trailing spaces add nothing to any span.  out must not overlap
+ *                buf.
+ *   text_len[n]  (NULL: not wanted) the bytes of each page's text.
+ *   pos          (NULL: not wanted) one uint32_t per output byte, indexed like
+ *                out: that byte's source position within its page, and L at the
+ *                padding.
+ *   status       (NULL: not wanted) the sums over the batch.
+ * Bytes outside [offsets[0], offsets[n]) are not written, in either array.
+ * cld_html_text is the host reference, no GPU; it reads the entity sections of
+ * the table blob on the host, as cld_hint_priors reads the hint sections.
+ * Tables without the HTML sections: CLD_EINVAL, from both entries.
+ * cld_html_text_device: every pointer in device memory of GPU `device` (8-byte
+ * aligned offsets, 4-byte aligned text_len and pos, 8-byte aligned status),
+ * enqueued on `stream` (NULL: the runtime's); asynchronous, the host reads no
+ * device word; none of the context's scratch is used and there is no
+ * workspace.  buf_bytes bounds d_offsets[n]: every offset is clamped to it, so
+ * no offsets word makes a kernel read outside d_buf[0, buf_bytes) or write
+ * outside the same range of d_out / d_pos; where the offsets go down the values
+ * are unspecified and the bounds still hold.  The caller keeps pages <=
+ * INT32_MAX bytes.  The status is written by the call's last kernel; the
+ * counts are integer sums, so the output is the same from run to run.  One
+ * wavefront takes one page.
+ * CLD_EINVAL: unknown flag bits; n > INT32_MAX; with n > 0 a NULL offsets; a
+ * NULL buf or out with buf_bytes > 0, whatever n is (the host entry has no
+ * buf_bytes: with n > 0 and offsets[n] > offsets[0]).  Otherwise n == 0: CLD_OK
+ * and a zero status.
+ *
+ * cld_chunks_to_page (the host reference, no GPU) / cld_chunks_to_page_device
+ * take chunk vectors that index the text -- from cld_detect_batch_device_vec on
+ * the text batch, or from cld_lines_to_chunks_device with doc_lines as chunk
+ * offsets -- and rewrite them to index the page.  Documents and vectors are
+ * read exactly as cld_chunk_totals defines them (the chunk_cap rule, the piece
+ * [s, e) clipped to [0, L)).  With P(x) = min(pos[offsets[i] + x], L) for x < L
+ * and P(L) = L, out_chunks[c] = {offset = P(s), bytes = max(P(e) - P(s), 0),
+ * lang1, pad = 0} for every existing chunk c of every document.  Pieces that
+ * tile the text therefore tile the page: a piece ends where the next text
+ * byte's source begins, so it takes the markup that follows it.  pos values
+ * are clamped: a hostile pos gives wrong numbers and no access outside the
+ * arrays.  out_chunks may be chunks itself.  The device entry: one wavefront
+ * per document, lanes over its chunks; no workspace; stream and device as above.
+ * CLD_EINVAL: as cld_chunk_totals, and NULL pos or out_chunks where there is
+ * a chunk to write (n > 0 and chunk_cap > 0). */
+#define CLD_HTMLTEXT_BLOCK_LF 1u        /* a block tag's separator byte is 0x0A */
+#define CLD_HTMLTEXT_BLOCK_TAGS \
+  "address article aside blockquote body br dd div dl dt fieldset figcaption figure footer form " \
+  "h1 h2 h3 h4 h5 h6 head header hr html li main nav ol option p pre script section style table tbody td " \
+  "tfoot th thead title tr ul"
+typedef struct cld_htmltext_status {
+  uint64_t text_bytes;                  /* sum of text_len */
+  uint64_t tags;                        /* tags reached */
+  uint32_t entities;                    /* entities decoded */
+  uint32_t dropped;                     /* undecodable '&' dropped */
+} cld_htmltext_status;
+int cld_html_text(const uint8_t* buf, const uint64_t* offsets, size_t n, uint32_t flags, uint8_t* out,
+                  int32_t* text_len, uint32_t* pos, cld_htmltext_status* status);
+int cld_html_text_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n, uint64_t buf_bytes,
+                         uint32_t flags, uint8_t* d_out, int32_t* d_text_len, uint32_t* d_pos,
+                         cld_htmltext_status* d_status, void* stream);
+int cld_chunks_to_page(const uint64_t* offsets, size_t n, const uint32_t* pos, const cld_chunk* chunks,
+                       uint64_t chunk_cap, const uint64_t* chunk_offsets, cld_chunk* out_chunks);
+int cld_chunks_to_page_device(int device, const uint64_t* d_offsets, size_t n, const uint32_t* d_pos,
+                              const cld_chunk* d_chunks, uint64_t chunk_cap, const uint64_t* d_chunk_offsets,
+                              cld_chunk* d_out_chunks, void* stream);
+
 /* The preparation step alone, on GPU 0 (host buffers): out_buf receives the
  * prepared documents back to back (capacity >= offsets[n]-offsets[0] + n
  * bytes), out_offsets[0..n] their offsets.  flags: CLD_FLAG_STRIP_EXTRAS and/or

@@ -22,6 +22,11 @@ Mirrors the reference's caller-facing interface for this path:
   split_lines / lines_to_chunks           a batch's lines as a new offsets array over the same text, and
                                           per-line results as one chunk vector per document (host references)
   split_lines_device / lines_to_chunks_device     the same over a batch in HBM: line-level detection
+  html_text / chunks_to_page              the text of HTML pages (tags to separators, entities decoded), page-aligned,
+                                          with each byte's position in its page; chunk vectors on the text
+                                          carried back to byte ranges of the page (host references)
+  html_text_device / chunks_to_page_device        the same over pages in HBM: HTML in front of the line,
+                                          chunk and group entries
   detect_language_scrubbed(text)          the repair on the host, then detect_language
 There is no CPU fallback: if the HIP library or a GPU is missing, calls raise.
 """
@@ -79,12 +84,19 @@ EXPORTS = ("detect_language", "cld_init", "cld_init_device", "cld_shutdown", "cl
            "cld_group_by_language_device", "cld_gather_docs_device", "cld_last_route_stats", "cld_chunk_work_bytes",
            "cld_chunk_totals", "cld_chunk_totals_device", "cld_gather_chunks", "cld_gather_chunks_device",
            "cld_lines_work_bytes", "cld_split_lines", "cld_split_lines_device", "cld_lines_to_chunks",
-           "cld_lines_to_chunks_device")
+           "cld_lines_to_chunks_device", "cld_html_text", "cld_html_text_device", "cld_chunks_to_page",
+           "cld_chunks_to_page_device")
 CHUNK_DTYPE = np.dtype([("offset", "<i4"), ("bytes", "<i4"), ("lang1", "<u2"), ("pad", "<u2")])   # cld_chunk
 LINES_JOIN_BLANK = 1       # include/cld_mi355x.h CLD_LINES_JOIN_BLANK: blank lines join the line after them
 LINES_TILE = 1024          # csrc/cld_kernels.h kLinesTile: the text bytes one wave of the split reads
 LINES_WGS = 256            # csrc/cld_kernels.h kLinesWgs: the split scans its tiles in at most this many ranges
 LINES_STATUS_DTYPE = np.dtype([("total_lines", "<u8"), ("max_line_bytes", "<u8")])   # cld_lines_status
+HTMLTEXT_BLOCK_LF = 1      # include/cld_mi355x.h CLD_HTMLTEXT_BLOCK_LF: a block tag's separator byte is 0x0A, not 0x20
+HTMLTEXT_STAGE = 2048      # csrc/cld_kernels.h kHtmlTextStage: pages up to this size are staged in LDS, longer ones read in place
+HTMLTEXT_CANDS = 256       # csrc/cld_kernels.h kHtmlTextCands: '<' / '&' candidates per segment of a page
+# include/cld_mi355x.h cld_htmltext_status
+HTMLTEXT_STATUS_DTYPE = np.dtype([("text_bytes", "<u8"), ("tags", "<u8"), ("entities", "<u4"), ("dropped", "<u4")])
+assert HTMLTEXT_STATUS_DTYPE.itemsize == 24
 
 
 class Hints(ctypes.Structure):
@@ -263,6 +275,10 @@ def lib():
         L.cld_split_lines_device.argtypes = [ctypes.c_int, vp, vp, sz, u64, u32, vp, vp, u64, vp, vp, vp, sz, vp]
         L.cld_lines_to_chunks.argtypes = [vp, vp, vp, u64, vp, sz, vp, u32, vp]
         L.cld_lines_to_chunks_device.argtypes = [ctypes.c_int, vp, vp, vp, u64, vp, sz, vp, u32, vp, vp]
+        L.cld_html_text.argtypes = [vp, vp, sz, u32, vp, vp, vp, vp]
+        L.cld_html_text_device.argtypes = [ctypes.c_int, vp, vp, sz, u64, u32, vp, vp, vp, vp, vp]
+        L.cld_chunks_to_page.argtypes = [vp, sz, vp, vp, u64, vp, vp]
+        L.cld_chunks_to_page_device.argtypes = [ctypes.c_int, vp, sz, vp, vp, u64, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -925,6 +941,65 @@ def lines_to_chunks_device(device, d_line_results_ptr, d_line_offsets_ptr, d_lin
                                           d_offsets_ptr, n, d_doc_lines_ptr, flags, d_chunks_ptr, stream_ptr)
     if rc != 0:
         raise CldError("cld_lines_to_chunks_device failed: %d" % rc)
+
+
+def html_text(buf, offsets, flags=0, pos=False):
+    """cld_html_text (the host reference, no GPU): the text of every HTML page of the batch, page-aligned ->
+    dict of out (uint8, indexed like buf: page i's text at offsets[i], then 0x20 to the page's end), text_len
+    int32[n], status (an HTMLTEXT_STATUS_DTYPE record) and, with pos=True, pos (uint32 per output byte: its
+    position in its page, the page's length at the padding).  flags: HTMLTEXT_BLOCK_LF."""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if len(offsets) < 1:
+        raise ValueError("need n + 1 offsets")
+    n = len(offsets) - 1
+    size = max(len(buf), int(offsets.max()))
+    got = {"out": np.zeros(size, np.uint8), "text_len": np.zeros(n, np.int32), "status": np.zeros(1, HTMLTEXT_STATUS_DTYPE)}
+    if pos:
+        got["pos"] = np.zeros(size, np.uint32)
+    rc = lib().cld_html_text(buf.ctypes.data, offsets.ctypes.data, n, flags, got["out"].ctypes.data,
+                             got["text_len"].ctypes.data, got["pos"].ctypes.data if pos else None,
+                             got["status"].ctypes.data)
+    if rc != 0:
+        raise CldError("cld_html_text failed: %d" % rc)
+    got["status"] = got["status"][0]
+    return got
+
+
+def html_text_device(device, d_buf_ptr, d_offsets_ptr, n, buf_bytes, d_out_ptr, flags=0, d_text_len_ptr=None,
+                     d_pos_ptr=None, d_status_ptr=None, stream_ptr=None):
+    """cld_html_text_device: every pointer in device memory (out uint8[buf_bytes], indexed like the pages and
+    not overlapping them; text_len int32[n], pos uint32[buf_bytes], status an HTMLTEXT_STATUS_DTYPE record,
+    each or None); no workspace; asynchronous on the stream.  flags: HTMLTEXT_BLOCK_LF."""
+    rc = lib().cld_html_text_device(device, d_buf_ptr, d_offsets_ptr, n, buf_bytes, flags, d_out_ptr, d_text_len_ptr,
+                                    d_pos_ptr, d_status_ptr, stream_ptr)
+    if rc != 0:
+        raise CldError("cld_html_text_device failed: %d" % rc)
+
+
+def chunks_to_page(offsets, pos, chunks, chunk_offsets, chunk_cap=None):
+    """cld_chunks_to_page (the host reference, no GPU): chunk vectors that index the text of html_text
+    (CHUNK_DTYPE and chunk_offsets, as for chunk_totals) rewritten to index the pages, through pos ->
+    CHUNK_DTYPE[chunk_cap]; chunks that do not exist stay zero."""
+    offsets, chunks, chunk_offsets, cap = _chunk_args(offsets, chunks, chunk_offsets, chunk_cap)
+    pos = np.ascontiguousarray(pos, dtype=np.uint32)
+    out = np.zeros(max(cap, 1), CHUNK_DTYPE)
+    rc = lib().cld_chunks_to_page(offsets.ctypes.data, len(offsets) - 1, pos.ctypes.data, chunks.ctypes.data, cap,
+                                  chunk_offsets.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise CldError("cld_chunks_to_page failed: %d" % rc)
+    return out[:cap]
+
+
+def chunks_to_page_device(device, d_offsets_ptr, n, d_pos_ptr, d_chunks_ptr, chunk_cap, d_chunk_offsets_ptr,
+                          d_out_chunks_ptr, stream_ptr=None):
+    """cld_chunks_to_page_device: every pointer in device memory (the pages' offsets, pos as html_text_device
+    wrote it, cld_chunk[chunk_cap] on the text, chunk_offsets uint64[n + 1], the output cld_chunk[chunk_cap],
+    which may be the input); asynchronous on the stream."""
+    rc = lib().cld_chunks_to_page_device(device, d_offsets_ptr, n, d_pos_ptr, d_chunks_ptr, chunk_cap,
+                                         d_chunk_offsets_ptr, d_out_chunks_ptr, stream_ptr)
+    if rc != 0:
+        raise CldError("cld_chunks_to_page_device failed: %d" % rc)
 
 
 def valid_prefix_host(doc):

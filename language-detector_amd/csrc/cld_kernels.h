@@ -273,6 +273,21 @@ hipError_t cld_launch_split_lines(const uint8_t* buf, const uint64_t* offs, uint
 hipError_t cld_launch_lines_to_chunks(const cld_result* res, const uint64_t* line_offsets, const uint32_t* line_doc,
                                       uint64_t line_cap, const uint64_t* offs, uint32_t n, const uint64_t* doc_lines,
                                       uint32_t group_flags, cld_chunk* chunks, hipStream_t s);
+// cld_html_text_device / cld_chunks_to_page_device (cld_htmltext.hip).  One wave
+// per page: pages of at most kHtmlTextStage bytes are staged in LDS, longer ones
+// read in place; a page is walked in segments of whole 64-byte windows holding
+// at most kHtmlTextCands '<' / '&' candidates.  No workspace.  buf_bytes bounds
+// offs[n]; n <= INT32_MAX.  cld_launch_html_text: text_len, pos, status each
+// nullable; status is zeroed on the stream, then summed into by the kernel;
+// max_wgs (0: 2048): a cap on the workgroups, so that a test makes every wave
+// take several pages at a small size.
+constexpr int kHtmlTextStage = 2048;
+constexpr int kHtmlTextCands = 256;
+hipError_t cld_launch_html_text(const DevTables* d_T, const uint8_t* buf, const uint64_t* offs, uint32_t n,
+                                uint64_t buf_bytes, uint32_t flags, uint8_t* out, int32_t* text_len, uint32_t* pos,
+                                cld_htmltext_status* status, uint32_t max_wgs, hipStream_t s);
+hipError_t cld_launch_chunks_to_page(const uint64_t* offs, uint32_t n, const uint32_t* pos, const cld_chunk* chunks,
+                                     uint64_t chunk_cap, const uint64_t* chunk_offs, cld_chunk* out, hipStream_t s);
 // ApplyHints (cld_hints.hip; compact_lang_det_impl.cc:1587-1684), one wave
 // per document: priors14 (14 per document, trimmed to 4, zero-padded),
 // boosts16 (the 16 langprobs enqueue() takes as `priors`) and special (the

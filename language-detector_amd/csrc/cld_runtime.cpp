@@ -31,6 +31,7 @@
 #include "cld_device.h"
 #include "cld_dynamic_data.h"
 #include "cld_hints.h"
+#include "cld_htmltext.h"
 #include "cld_kernels.h"
 #include "cld_owned.h"
 #include "cld_valid_rule.h"
@@ -2969,6 +2970,101 @@ int cld_lines_to_chunks_device(int device, const cld_result* d_line_results, con
   HIP_OK(hipSetDevice(d->id));
   HIP_OK(cld_launch_lines_to_chunks(d_line_results, d_line_offsets, d_line_doc, line_cap, d_offsets, (uint32_t)n,
                                     d_doc_lines, group_flags, d_chunks, stream ? (hipStream_t)stream : d->stream));
+  return CLD_OK;
+}
+
+namespace {
+// Test hook of cld_html_text_device, read once per process: CLD_HTMLTEXT_WGS=k caps
+// the kernel's workgroups at k, so that every wave takes several pages at a small
+// batch (tests/test_gpu_htmltext.py); 0: no cap.
+uint32_t htmltext_max_wgs() {
+  static const uint32_t v = (uint32_t)std::max<long>(env_long("CLD_HTMLTEXT_WGS", 0), 0);
+  return v;
+}
+bool to_page_args_bad(const uint64_t* offsets, size_t n, const uint32_t* pos, const cld_chunk* chunks, uint64_t chunk_cap,
+                      const uint64_t* chunk_offsets, const cld_chunk* out_chunks) {
+  return chunk_args_bad(offsets, n, chunks, chunk_cap, chunk_offsets) || (n > 0 && chunk_cap > 0 && (!pos || !out_chunks));
+}
+}  // namespace
+
+// The host reference of the extraction (cld_htmltext.cpp): one sequential walk per page.
+int cld_html_text(const uint8_t* buf, const uint64_t* offsets, size_t n, uint32_t flags, uint8_t* out,
+                  int32_t* text_len, uint32_t* pos, cld_htmltext_status* status) {
+  if ((flags & ~CLD_HTMLTEXT_BLOCK_LF) != 0 || n > 0x7FFFFFFFu || (n > 0 && !offsets) ||
+      (n > 0 && offsets[n] > offsets[0] && (!buf || !out)))
+    return CLD_EINVAL;
+  {
+    std::lock_guard<std::mutex> lk(g_init_mu);
+    if (int rc = host_tables(nullptr)) return rc;
+  }
+  std::shared_lock<std::shared_mutex> tl(g_swap_mu);
+  if (!g_tab.offs.ent_names) return CLD_EINVAL;     // tables without the HTML sections
+  const uint8_t* blob = g_tab.blob.data();
+  cld::EntityView v;
+  v.names = blob + (uintptr_t)g_tab.offs.ent_names;
+  v.values = reinterpret_cast<const int32_t*>(blob + (uintptr_t)g_tab.offs.ent_values);
+  v.cp1252 = reinterpret_cast<const uint32_t*>(blob + (uintptr_t)g_tab.offs.cp1252);
+  cld_htmltext_status st = {0, 0, 0, 0};
+  for (size_t i = 0; i < n; ++i) {
+    const int64_t L = std::min<int64_t>(host_doc_len(offsets, i), 0x7FFFFFFF);
+    const uint64_t a = offsets[i];
+    const int64_t q = L ? cld::html_text_page(v, buf + a, L, flags, out + a, pos ? pos + a : nullptr, &st) : 0;
+    if (text_len) text_len[i] = (int32_t)q;
+  }
+  if (status) *status = st;
+  return CLD_OK;
+}
+
+int cld_html_text_device(int device, const uint8_t* d_buf, const uint64_t* d_offsets, size_t n, uint64_t buf_bytes,
+                         uint32_t flags, uint8_t* d_out, int32_t* d_text_len, uint32_t* d_pos,
+                         cld_htmltext_status* d_status, void* stream) {
+  if ((flags & ~CLD_HTMLTEXT_BLOCK_LF) != 0 || n > 0x7FFFFFFFu || (n > 0 && (!d_offsets || ((uintptr_t)d_offsets & 7))) ||
+      (buf_bytes > 0 && (!d_buf || !d_out)) || ((uintptr_t)d_text_len & 3) || ((uintptr_t)d_pos & 3) ||
+      ((uintptr_t)d_status & 7))
+    return CLD_EINVAL;
+  int rc = cld_init(nullptr, 0);
+  if (rc) return rc;
+  if (device < 0 || device >= (int)g_devs.size()) return CLD_EINVAL;
+  Device* d = g_devs[device];
+  if (!d->T.ent_names) return CLD_EINVAL;           // tables without the HTML sections
+  HIP_OK(hipSetDevice(d->id));
+  // (no scratch of the context is used: nothing to serialise with other batches)
+  HIP_OK(cld_launch_html_text(d->d_T, d_buf, d_offsets, (uint32_t)n, buf_bytes, flags, d_out, d_text_len, d_pos, d_status,
+                              htmltext_max_wgs(), stream ? (hipStream_t)stream : d->stream));
+  return CLD_OK;
+}
+
+int cld_chunks_to_page(const uint64_t* offsets, size_t n, const uint32_t* pos, const cld_chunk* chunks,
+                       uint64_t chunk_cap, const uint64_t* chunk_offsets, cld_chunk* out_chunks) {
+  if (to_page_args_bad(offsets, n, pos, chunks, chunk_cap, chunk_offsets, out_chunks)) return CLD_EINVAL;
+  for (size_t i = 0; i < n; ++i) {
+    const int64_t len = host_doc_len(offsets, i);
+    const uint32_t* dp = pos + offsets[i];
+    auto P = [&](int64_t x) { return x < len ? std::min<int64_t>(dp[x], len) : len; };
+    const uint64_t end = std::min(chunk_offsets[i + 1], chunk_cap);
+    for (uint64_t c = chunk_offsets[i]; c < end; ++c) {
+      const HostPiece p = host_piece(chunks[c], len);
+      const int64_t ps = P(p.s), pe = P(p.e);
+      const cld_chunk r = {(int32_t)std::min<int64_t>(ps, 0x7FFFFFFF),
+                           (int32_t)std::min<int64_t>(std::max<int64_t>(pe - ps, 0), 0x7FFFFFFF), chunks[c].lang1, 0};
+      out_chunks[c] = r;
+    }
+  }
+  return CLD_OK;
+}
+
+int cld_chunks_to_page_device(int device, const uint64_t* d_offsets, size_t n, const uint32_t* d_pos,
+                              const cld_chunk* d_chunks, uint64_t chunk_cap, const uint64_t* d_chunk_offsets,
+                              cld_chunk* d_out_chunks, void* stream) {
+  if (to_page_args_bad(d_offsets, n, d_pos, d_chunks, chunk_cap, d_chunk_offsets, d_out_chunks)) return CLD_EINVAL;
+  int rc = cld_init(nullptr, 0);
+  if (rc) return rc;
+  if (device < 0 || device >= (int)g_devs.size()) return CLD_EINVAL;
+  if (n == 0 || chunk_cap == 0) return CLD_OK;
+  Device* d = g_devs[device];
+  HIP_OK(hipSetDevice(d->id));
+  HIP_OK(cld_launch_chunks_to_page(d_offsets, (uint32_t)n, d_pos, d_chunks, chunk_cap, d_chunk_offsets, d_out_chunks,
+                                   stream ? (hipStream_t)stream : d->stream));
   return CLD_OK;
 }
 
